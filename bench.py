@@ -15,7 +15,13 @@ the step advances the hidden state in place instead of cloning it, same results)
 backward captured once in a HIP graph and replayed (torch.cuda.CUDAGraph, in process); the same loop run
 eagerly, with donated and with functional (reference-default) state, is reported beside it (`variants`).
 
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, `config`);
+`--full` adds everything else (`value_spread`, `variants`, `roofline`, `kernel_table`, `cpu_baseline`, ...).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (inputs are seeded: two builds
+run with the same arguments can be compared output for output).
+
   python bench.py --gpus N --steps K --warmup W        # N > 1 without WORLD_SIZE: spawns N ranks
+  python bench.py --full                               # the headline and every side measurement
   python bench.py --config cfg3|cfg4|cfg5 ...          # the other BASELINE configs, same JSON contract
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
@@ -136,13 +142,19 @@ def make_obs(c, rank, device):
     return obs.to(device)
 
 
-def rollout(mem, obs, bucket=None, weight=1.0):
+def rollout(mem, obs, bucket=None, weight=1.0, keep=None):
+    """One bench step.  `keep` (a dict): receives what the caller of the step gets back - the belief states,
+    the loss and the final hidden state (inside a captured graph: the graph's static tensors)."""
     import torch
     hidden, outs = None, []
     for t in range(obs.shape[0]):
         mx, hidden = mem(obs[t], hidden)
         outs.append(mx)
-    loss = torch.stack(outs).mean()
+    belief = torch.stack(outs)
+    loss = belief.mean()
+    if keep is not None:
+        keep.update(belief=belief, loss=loss, hidden=hidden)
+    del belief          # (without `keep`: freed ahead of the backward)
     loss.backward()
     if bucket is not None:
         bucket.all_reduce_mean(weight)
@@ -618,11 +630,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--T", type=int, default=None, help="rollout length (cfg2: 128 fills the graph)")
-    ap.add_argument("--repeats", type=int, default=5, help="extra timed blocks of K steps for value_spread")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="time the eager loop instead of the graph replay")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (belief states, loss, final hidden "
+                         "state, parameter gradients; rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: value_spread, variants, roofline, kernel "
+                         "table, CPU baseline (without it: set-up, warm-up, the timed steps and the result line)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: extra timed blocks of K steps for value_spread")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the variants (cfg4: the stepwise leg) - for profiles of the headline leg alone")
+                    help="--full: skip the variants (cfg4: the stepwise leg) - for profiles of the headline leg alone")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -684,6 +702,87 @@ def spread_of(times, states_per_block):
             "note": "belief-states/s of each timed block of `steps` bench steps (the first block is `value`)"}
 
 
+def dense_config(c, T, can_donate, graph, world):
+    """the `config` block of a dense line"""
+    return {"workload": c["text"] + ", T=%d; one bench step = one rollout through the per-step drop-in call "
+                                    "surface `for t: mx, m = gcm(obs[t], m)` + backward" % T,
+            "B_per_gpu": c["B"], "graph_size": c["N"], "obs": c["F"], "hidden": c["H"], "T": T,
+            "state": "donated (DenseGCM(donate_state=True): hidden state advanced in place)" if can_donate
+                     else "functional",
+            "launch": "eager" if graph is None else "HIP graph of the loop + backward, captured once "
+                                                    "in process, replayed per bench step",
+            "parallelism": f"dp{world} (batch-sharded, 1 flat-bucket all-reduce per backward)"}
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step returned, as .npy files
+# ------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def named_grads(mods):
+    """{"grad_<module index>_<parameter name>": gradient} of the modules' parameters that hold one"""
+    return {"grad_%d_%s" % (i, n.replace(".", "_")): p.grad for i, m in enumerate(mods)
+            for n, p in m.named_parameters() if p.grad is not None}
+
+
+def sample_index(name, numel, k):
+    """a fixed, seeded choice of k of numel flat positions (sorted), the same for every run and build"""
+    import zlib
+    import numpy as np
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.sort(rng.choice(numel, size=k, replace=False))
+
+
+def host_arrays(tensors):
+    """{name: tensor} -> {name: float32 / float64 ndarray}; a sparse tensor gives <name>_indices and <name>_values,
+    integer tensors are stored as float64 (exact), empty tensors are left out"""
+    import torch
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.is_sparse:
+            t = t.coalesce()
+            out.update(host_arrays({name + "_indices": t.indices(), name + "_values": t.values()}))
+            continue
+        if t.numel() == 0:
+            continue
+        t = t.cpu()
+        out[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+    return out
+
+
+def budget_arrays(arrays, budget=DUMP_BUDGET_BYTES):
+    """Fit {name: ndarray} into `budget` bytes: arrays of up to 1 MB are kept whole; when the whole set exceeds the
+    budget, every larger array is replaced by a fixed, seeded sample of its flattened elements (sample_index), all
+    at the same fraction.  -> ({name: ndarray}, {name: (numel, kept)} of the sampled ones)"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= budget:
+        return dict(arrays), {}
+    small = {k: a for k, a in arrays.items() if a.nbytes <= 1 << 20}
+    big = {k: a for k, a in arrays.items() if a.nbytes > 1 << 20}
+    frac = (budget - sum(a.nbytes for a in small.values())) / sum(a.nbytes for a in big.values())
+    out, sampled = dict(small), {}
+    for k, a in big.items():
+        keep = max(1, int(a.size * frac * 0.99))
+        out[k] = a.reshape(-1)[sample_index(k, a.size, keep)]
+        sampled[k] = (a.size, keep)
+    return out, sampled
+
+
+def write_outputs(path, tensors):
+    """--dump-outputs: every tensor as <path>/<name>.npy (float32 / float64), at most DUMP_BUDGET_BYTES in all"""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays, sampled = budget_arrays(host_arrays(tensors))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    for k, (n, kept) in sampled.items():
+        print("dump-outputs: %s sampled, %d of %d elements" % (k, kept, n), file=sys.stderr)
+
+
 def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
     import torch
     from gcm import parallel
@@ -709,17 +808,18 @@ def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
     # all-reduce when the backend can be captured (RCCL); else the collective follows each replay eagerly.
     comm = {"captured": False, "launches_outside_graph": 0, "bucket_floats": bucket.numel}
     graph = None
+    keep = {} if args.dump_outputs else None     # what the timed step returns to its caller
     if not args.no_graph and world > 1:
         bucket.attach()
 
-        def body(with_comm):
+        def body(with_comm, keep=None):
             bucket.zero()
-            rollout(mem, obs)
+            rollout(mem, obs, keep=keep)
             if with_comm:
                 bucket.all_reduce_mean(weight)
         if os.environ.get("GCM_BENCH_CAPTURE_COMM", "1") == "1" and dist_backend() == "nccl":
             try:
-                graph = capture(lambda: body(True), bucket.zero)
+                graph = capture(lambda: body(True, keep), bucket.zero)
                 comm["captured"] = True
             except Exception as e:      # (reported; the eager collective is the fallback)
                 comm["capture_error"] = "%s: %s" % (type(e).__name__, str(e)[:160])
@@ -734,9 +834,9 @@ def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
                 comm["capture_error"] = "another rank failed to capture the collective"
                 graph = None
         if graph is None:
-            graph = capture(lambda: body(False), bucket.zero)
+            graph = capture(lambda: body(False, keep), bucket.zero)
     elif not args.no_graph:
-        graph = capture(lambda: rollout(mem, obs), zero)
+        graph = capture(lambda: rollout(mem, obs, keep=keep), zero)
     # what rank 0 profiles ALONE further down must hold no collective (the other ranks have left by then: a replayed
     # all-reduce would wait for them forever): with the collective captured, a twin of the graph without it
     graph_prof = graph
@@ -749,10 +849,29 @@ def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
             if world > 1 and not comm["captured"]:
                 bucket.all_reduce_mean(weight)
         else:
-            rollout(mem, obs, bucket, weight)
+            rollout(mem, obs, bucket, weight, keep=keep)
+            if keep is not None:
+                keep["grads"] = named_grads(mods)
             zero()
 
     dt = timed(step, args.steps, args.warmup)
+    if keep is not None and rank == 0:
+        h_nodes, h_adj, h_weights, h_count = keep["hidden"]
+        # (graph replay: the parameters' gradients are the graph's static tensors, rewritten by every replay)
+        write_outputs(args.dump_outputs, dict(
+            {"belief": keep["belief"], "loss": keep["loss"], "hidden_nodes": h_nodes, "hidden_adj": h_adj,
+             "hidden_weights": h_weights, "hidden_num_nodes": h_count},
+            **(keep["grads"] if graph is None else named_grads(mods))))
+    if not args.full:
+        bits = int(mem._flag_word(device).item())
+        assert not (bits & 6), f"kernels flagged {bits}"
+        if rank == 0:
+            line.update({"value": world * B * T * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
+                         "config": dense_config(c, T, can_donate, graph, world)})
+            if name != "cfg2":
+                line["metric"] = "belief-states/sec (BxT) DenseGCM fwd+bwd, graph_size=128 (%s)" % name
+            print(json.dumps(line))
+        return
     blocks = [dt] + [timed(step, args.steps, 0) for _ in range(max(0, args.repeats))]
     flags = mem._flag_word(device)
     bits = int(flags.item())
@@ -1241,14 +1360,7 @@ def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
     line.update({
         "value": states / dt, "ms_per_step": ms_per_step,
         "value_spread": spread_of(blocks, world * B * T * args.steps),
-        "config": {"workload": c["text"] + ", T=%d; one bench step = one rollout through the per-step drop-in call "
-                                           "surface `for t: mx, m = gcm(obs[t], m)` + backward" % T,
-                   "B_per_gpu": B, "graph_size": N, "obs": F, "hidden": H, "T": T,
-                   "state": "donated (DenseGCM(donate_state=True): hidden state advanced in place)" if can_donate
-                            else "functional",
-                   "launch": "eager" if graph is None else "HIP graph of the loop + backward, captured once "
-                                                           "in process, replayed per bench step",
-                   "parallelism": f"dp{world} (batch-sharded, 1 flat-bucket all-reduce per backward)"},
+        "config": dense_config(c, T, can_donate, graph, world),
         "variants": {k: (round(v, 1) if isinstance(v, float) else ([round(x, 1) for x in v] if isinstance(v, list) else v))
                      for k, v in variants.items()},
         "variants_note": "belief-states/s of the same workload: the eager per-step loop with donated / functional "
@@ -1312,6 +1424,13 @@ def bench_dense(args, c, line, rank, world, device, timed, weight, traffic):
     print(json.dumps(line))
 
 
+def sparse_config(c, world):
+    """the `config` block of the sparse line"""
+    return {"workload": c["text"] + "; one bench step = one SparseGCM call on [B, 512, F] + backward, eager",
+            "B_per_gpu": c["B"], "graph_size": c["N"], "obs": c["F"], "hidden": c["H"], "T": c["N"],
+            "parallelism": f"dp{world} (batch-sharded, 1 flat-bucket all-reduce per backward)"}
+
+
 def bench_sparse(args, c, line, rank, world, device, timed, weight, traffic):
     """cfg4: SparseGCM + TemporalEdge([1]).  One bench step = one call over whole episodes
     (x [B, N, F], taus = N: B*N belief states) + backward."""
@@ -1330,13 +1449,29 @@ def bench_sparse(args, c, line, rank, world, device, timed, weight, traffic):
     x = torch.rand(B, N, F, generator=gen).to(device)
     taus = torch.full((B,), N, dtype=torch.long, device=device)
 
+    keep = {} if args.dump_outputs else None     # what the timed step returns to its caller
+
     def oneshot():
-        out, _ = mem(x, taus, None)
-        out.mean().backward()
+        out, hidden = mem(x, taus, None)
+        loss = out.mean()
+        loss.backward()
         bucket.all_reduce_mean(weight)
+        if keep is not None:
+            keep.update(out=out, loss=loss, hidden=hidden, grads=named_grads([g]))
         g.zero_grad(set_to_none=True)
 
     dt = timed(oneshot, args.steps, args.warmup)
+    if keep is not None and rank == 0:
+        h_nodes, h_adj, h_count = keep["hidden"]
+        write_outputs(args.dump_outputs, dict({"out": keep["out"], "loss": keep["loss"], "hidden_nodes": h_nodes,
+                                               "hidden_adj": h_adj, "hidden_num_nodes": h_count}, **keep["grads"]))
+    metric = "belief-states/sec (BxT) SparseGCM fwd+bwd, graph_size=512 F=32 (cfg4)"
+    if not args.full:
+        if rank == 0:
+            line.update({"metric": metric, "value": world * B * N * args.steps / dt,
+                         "ms_per_step": dt / args.steps * 1e3, "config": sparse_config(c, world)})
+            print(json.dumps(line))
+        return
     blocks = [dt] + [timed(oneshot, args.steps, 0) for _ in range(max(0, args.repeats))]
     if external_profiler_attached():      # (see bench_dense)
         if rank == 0:
@@ -1401,12 +1536,10 @@ def bench_sparse(args, c, line, rank, world, device, timed, weight, traffic):
         elif d["us_per_call"] > 0.02 * gpu_us:
             pmc_missing.append(k)
     line.update({
-        "metric": "belief-states/sec (BxT) SparseGCM fwd+bwd, graph_size=512 F=32 (cfg4)",
+        "metric": metric,
         "value": states / dt, "ms_per_step": ms_per_step,
         "value_spread": spread_of(blocks, world * B * N * args.steps),
-        "config": {"workload": c["text"] + "; one bench step = one SparseGCM call on [B, 512, F] + backward, eager",
-                   "B_per_gpu": B, "graph_size": N, "obs": F, "hidden": H, "T": N,
-                   "parallelism": f"dp{world} (batch-sharded, 1 flat-bucket all-reduce per backward)"},
+        "config": sparse_config(c, world),
         "variants": {k: round(v, 1) for k, v in variants.items()},
         "variants_note": "stepwise: the same episodes one node per call (taus = 1, %d calls from hidden = None) + one "
                          "backward, default settings (finite_check = 'sync'): every call on the chain's caches "

@@ -1,5 +1,7 @@
 """Pin the CPU oracle against golden vectors captured from the reference
 (tests/golden/make_golden.py).  CPU only."""
+import copy
+
 import pytest
 import torch
 
@@ -138,6 +140,22 @@ SPARSE = ["g8_sparse_oneshot", "g8_sparse_oneshot_2hop", "g8_sparse_stepwise",
           "g8_sparse_ragged", "g8_sparse_ragged_2hop", "g16_sparse_aux", "g16_sparse_aux_overlap"]
 
 
+def _sparse_rollout(fx, obs, gnn, sel, aux):
+    m = fx.meta
+    B = m["B"]
+    hidden, outs, pos = None, [], torch.zeros(B, dtype=torch.long)
+    for taus in fx["taus"]:
+        t = int(taus.max())
+        x = torch.zeros(B, t, m["F"], dtype=obs.dtype)
+        for b in range(B):
+            x[b, : taus[b]] = obs[b, pos[b]: pos[b] + taus[b]]
+        out, hidden = osp.sparse_step(x, taus, hidden, gnn, graph_size=m["N"], edge_selectors=sel,
+                                      max_hops=m["max_hops"], aux_edge_selectors=aux)
+        outs.append(out)
+        pos = pos + taus
+    return outs, hidden
+
+
 @pytest.mark.parametrize("name", SPARSE)
 def test_sparse_oracle_matches_reference(name):
     fx = Fixture(name)
@@ -147,21 +165,21 @@ def test_sparse_oracle_matches_reference(name):
     sel = osp.TemporalEdge(m["hops"])
     aux = osp.TemporalEdge(m["aux_hops"]) if m.get("aux_hops") else None
     obs = fx["obs"].clone().requires_grad_(True)
-    B = m["B"]
-    hidden, outs, pos = None, [], torch.zeros(B, dtype=torch.long)
-    for taus in fx["taus"]:
-        t = int(taus.max())
-        x = torch.zeros(B, t, m["F"])
-        for b in range(B):
-            x[b, : taus[b]] = obs[b, pos[b]: pos[b] + taus[b]]
-        out, hidden = osp.sparse_step(x, taus, hidden, gnn, graph_size=m["N"], edge_selectors=sel,
-                                      max_hops=m["max_hops"], aux_edge_selectors=aux)
-        outs.append(out)
-        pos = pos + taus
+    outs, hidden = _sparse_rollout(fx, obs, gnn, sel, aux)
     loss = sum(o.sum() for o in outs) / sum(o.numel() for o in outs)
     loss.backward()
+    # The fixtures were captured on one BLAS code path; where the host's math library takes another, the fp32
+    # sums run in another order.  atol: 3x the reference's own fp32 distance from the same rollout in float64
+    # (floor 1e-6), the rule tests/_golden.py applies to the GPU path.
+    torch.set_default_dtype(torch.float64)      # (the oracle's zero state)
+    try:
+        with torch.no_grad():
+            outs64, _ = _sparse_rollout(fx, fx["obs"].double(), copy.deepcopy(gnn).double(), sel, aux)
+    finally:
+        torch.set_default_dtype(torch.float32)
     for i, o in enumerate(outs):
-        torch.testing.assert_close(o, fx[f"out{i}"], rtol=1e-6, atol=1e-6)
+        atol = max(1e-6, 3.0 * float((fx[f"out{i}"].double() - outs64[i]).abs().max()))
+        torch.testing.assert_close(o, fx[f"out{i}"], rtol=1e-6, atol=atol)
     assert torch.equal(hidden[0], fx["hT_nodes"])
     assert torch.equal(hidden[1].coalesce().indices(), fx["hT_adj_indices"])   # bit exact
     assert torch.equal(hidden[2], fx["hT_T"])

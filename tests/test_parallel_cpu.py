@@ -21,8 +21,9 @@ def _free_port():
 def _worker(rank, world, port, q):
     for p in (ROOT, os.path.join(ROOT, "graph-conv-memory_amd")):
         sys.path.insert(0, p)
+    # (GCM_SINGLE_DEVICE: on a host with one GPU, rank 1 must not select a second device)
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), GCM_SINGLE_DEVICE="1")
     from gcm import parallel
     from oracle import dense as od
 

@@ -89,7 +89,7 @@ def test_bench_cfg5_two_ranks():
     env = dict(os.environ, GCM_SINGLE_DEVICE="1", GCM_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--gpus", "2",
-            "--steps", "2", "--warmup", "1", "--T", "12", "--repeats", "1", "--no-cpu-baseline"]
+            "--steps", "2", "--warmup", "1", "--T", "12", "--full", "--repeats", "1", "--no-cpu-baseline"]
     p = subprocess.run(argv, env=env, capture_output=True, timeout=600)
     if p.returncode != 0:
         # (this child failed once inside a full-suite run: bench.py then still traced its T = 2N graph in process, and
@@ -171,7 +171,7 @@ def test_bench_cfg5_two_gpus_over_rccl():
     for k in ("WORLD_SIZE", "GCM_SINGLE_DEVICE", "GCM_DIST_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--gpus", "2",
-                        "--steps", "2", "--warmup", "1", "--T", "12", "--repeats", "1", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--T", "12", "--full", "--repeats", "1", "--no-cpu-baseline"],
                        env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])

@@ -28,7 +28,7 @@ for part in $PARTS; do
     bench)   # the JSON line of every config, unprofiled
       for cfg in cfg2 cfg3 cfg4 cfg5 dense_edge; do
         # (its own log name: the stats part below writes bench_$cfg.log; a failed run must not leave the previous line in place)
-        if python3 bench.py --config $cfg > "$OUT/benchline_$cfg.log" 2>&1; then
+        if python3 bench.py --full --config $cfg > "$OUT/benchline_$cfg.log" 2>&1; then
           tail -1 "$OUT/benchline_$cfg.log" > "$OUT/${TAG}_bench_$cfg.json"; echo "bench $cfg done"
         else
           rm -f "$OUT/${TAG}_bench_$cfg.json"; echo "bench $cfg FAILED (see benchline_$cfg.log)"
@@ -36,11 +36,11 @@ for part in $PARTS; do
       done ;;
     stats)   # --kernel-trace --stats of the same command (cfg4: the one-shot headline leg alone, and both legs)
       # (under rocprofv3 bench.py runs its timed region alone - the profiler's kernel statistics are the headline's)
-      stats bench_cfg2 bench.py --config cfg2 --no-cpu-baseline
-      stats bench_cfg3 bench.py --config cfg3 --no-cpu-baseline
-      stats bench_cfg4 bench.py --config cfg4 --no-cpu-baseline
-      stats bench_cfg5 bench.py --config cfg5 --no-cpu-baseline
-      stats bench_dense_edge bench.py --config dense_edge --no-cpu-baseline ;;
+      stats bench_cfg2 bench.py --full --config cfg2 --no-cpu-baseline
+      stats bench_cfg3 bench.py --full --config cfg3 --no-cpu-baseline
+      stats bench_cfg4 bench.py --full --config cfg4 --no-cpu-baseline
+      stats bench_cfg5 bench.py --full --config cfg5 --no-cpu-baseline
+      stats bench_dense_edge bench.py --full --config dense_edge --no-cpu-baseline ;;
     stats_tools)
       stats euclid_full tools/prof_euclid_full.py
       stats euclid_tp tools/prof_euclid_tp.py
@@ -76,10 +76,10 @@ for part in $PARTS; do
     dense)   # the dense-materialised regime (bench.py --config dense_edge): the general live-row kernel with every row
              # live (the column-write cached step switched off) - kernel statistics of the same bench command, then
              # HBM traffic and SQ counters of both forms from tools/pmc_dense_run.py (side profile: its own tag)
-      GCM_COL_CACHE=0 python3 bench.py --config dense_edge --no-cpu-baseline > "$OUT/bench_dense_edge_general.log" 2>&1 \
+      GCM_COL_CACHE=0 python3 bench.py --full --config dense_edge --no-cpu-baseline > "$OUT/bench_dense_edge_general.log" 2>&1 \
         && tail -1 "$OUT/bench_dense_edge_general.log" > "$OUT/${TAG}_bench_dense_edge_general.json"
       export GCM_COL_CACHE=0
-      stats bench_dense_edge_general bench.py --config dense_edge --no-cpu-baseline
+      stats bench_dense_edge_general bench.py --full --config dense_edge --no-cpu-baseline
       unset GCM_COL_CACHE
       pmc FETCH_SIZE tools/pmc_dense_run.py
       pmc WRITE_SIZE tools/pmc_dense_run.py
