@@ -24,6 +24,8 @@ STEP_IMG_V4 = 64          # ... its weights as 16-byte loads (the image's second
 BPTT_MANY_ROWS = 128      # gcm_dense_rows_bptt: records with many live rows per graph (DenseEdge)
 STEP_ONE_WAVE = 512       # gcm_dense_rows_step_cached: the one-wave kernel where the two-wave form exists (A/B)
 STEP_FOUR_WAVES = 256     # gcm_dense_rows_step_colcache: the four-wave kernel where the eight-wave form exists (A/B)
+SPATIAL_RADIUS_CAUSAL, SPATIAL_RADIUS_ALL, SPATIAL_KNN = 0, 1, 2   # gcm_spatial_count / _fill modes
+SPATIAL_MAX_COLS = 32
 
 ABI_VERSION = 6           # include/gcm_hip.h: GCM_ABI_VERSION
 
@@ -185,6 +187,9 @@ PROTOTYPES = {
     "gcm_dense_rollout_bwd_batched_workspace_bytes": (_Z, [_I] * 6),
     "gcm_dense_rollout_bwd": (_I, [_P] * 9 + [_I] + [_P] * 3 + [_I] + [_P] * 8 + [_Z] + [_I] * 6
                               + [_P]),
+    "gcm_spatial_supported": (_I, [_I] * 5),
+    "gcm_spatial_count": (_I, [_P] * 4 + [_I, _I, _F, _I] + [_P] * 3 + [_I] * 3 + [_P]),
+    "gcm_spatial_fill": (_I, [_P] * 4 + [_I, _I, _F] + [_P] * 4 + [_L] + [_I] * 3 + [_P]),
 }
 
 

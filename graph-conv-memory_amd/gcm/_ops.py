@@ -1648,3 +1648,37 @@ class _SegmentSoftmax(torch.autograd.Function):
 
 def segment_softmax(logits, tau, noise, edges):
     return _SegmentSoftmax.apply(logits, tau, noise, edges)
+
+
+# ---------------------------------------------------------------------------
+# sparse spatial selectors (src/gcm/sparse_edge_selectors/spatial.py)
+# ---------------------------------------------------------------------------
+def spatial_edges(nodes, T, taus, cols, mode, radius=0.0, k=0):
+    """COO indices [3, E] (batch, sink, source) of SpatialRadiusEdge / SpatialKNNEdge in coalesced order, and the
+    per-graph edge offsets [B+1].  cols: host list of position columns; mode: _hip.SPATIAL_*.  One readback (E and
+    max(T + tau), the overflow check)."""
+    if nodes.dtype != _f32:
+        raise TypeError(f"spatial selector: the kernels read float32 node features, got {nodes.dtype}")
+    nodes, T, taus = nodes.detach().contiguous(), T.to(_i64).contiguous(), taus.to(_i64).contiguous()
+    _hip.on_device(nodes, T, taus)
+    B, N, F = nodes.shape
+    P = len(cols)
+    if not _hip.lib().gcm_spatial_supported(mode, B, N, F, P):
+        raise NotImplementedError(
+            f"spatial selector: {P} position columns at graph size {N} are beyond the kernels' limits "
+            f"(P <= {_hip.SPATIAL_MAX_COLS}, (P + 1) * N * 4 bytes of LDS <= 160 KB, N <= 4096 for kNN)")
+    dev = nodes.device
+    arr = (ctypes.c_int32 * max(P, 1))(*cols)
+    row_off = torch.empty(B, N, dtype=torch.int32, device=dev)
+    kth = torch.empty(B, N, dtype=_i64, device=dev) if mode == _hip.SPATIAL_KNN else None
+    edge_off = torch.empty(B + 2, dtype=_i64, device=dev)
+    _call("gcm_spatial_count", _hip.ptr(nodes), _hip.ptr(T), _hip.ptr(taus), ctypes.addressof(arr), P, mode,
+          float(radius), int(k), _hip.ptr(row_off), _hip.ptr(kth), _hip.ptr(edge_off), B, N, F, _hip.stream())
+    E, max_total = (int(v) for v in edge_off[B:].tolist())                # the one readback
+    if max_total > N:
+        raise IndexError(f"spatial selector: a graph holds {max_total} nodes, more than the node matrix's {N}")
+    idx = torch.empty(3, E, dtype=_i64, device=dev)
+    _call("gcm_spatial_fill", _hip.ptr(nodes), _hip.ptr(T), _hip.ptr(taus), ctypes.addressof(arr), P, mode,
+          float(radius), _hip.ptr(row_off), _hip.ptr(kth), _hip.ptr(edge_off), _hip.ptr(idx) if E else None, E,
+          B, N, F, _hip.stream())
+    return idx, edge_off[:B + 1]

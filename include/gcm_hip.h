@@ -1131,6 +1131,36 @@ int gcm_segment_softmax_bwd(const float* g_soft, const float* soft, const float*
                             float* g_logits, float* g_tau_rows, int64_t S, int64_t E,
                             gcm_stream_t stream);
 
+/* ---- sparse spatial selectors (src/gcm/sparse_edge_selectors/spatial.py) -------------- */
+
+/* Graph b holds T_b stored and tau_b new nodes (n_b = T_b + tau_b); pos = nodes[b, :, cols[0:P]] (cols: a HOST
+ * array of P column indices in [0, F), passed by value like the hops of gcm_sparse_temporal_count).  d2(i, j) =
+ * sum over p in order of (pos_i,p - pos_j,p)^2 in fp32 without contraction.  Edges (batch, sink, source):
+ *   GCM_SPATIAL_RADIUS_CAUSAL  sink i new, source j < i,              sqrt(d2) < radius (correctly rounded sqrt)
+ *   GCM_SPATIAL_RADIUS_ALL     sink j in [0, n_b), source i new,      sqrt(d2) < radius (self edges included)
+ *   GCM_SPATIAL_KNN            sink i new, source j < i among the k smallest keys (d2 bits << 32 | j) of i over
+ *                              all of [0, n_b) (i itself and the later new nodes are candidates too)
+ * No edges at all when max_b n_b <= 1 (spatial.py:30, 82).
+ * count: row_off [B, N] int32 (edges of graph b before sink row r, for the rows of the mode), kth [B, N] (kNN only:
+ *        the row's k-th smallest key, ~0 when k >= n_b; NULL otherwise) and edge_off [B+2]: [0, B] the per-graph
+ *        edge offsets (edge_off[B] = E), edge_off[B+1] = max_b (T_b + tau_b) (> N: the caller's overflow error;
+ *        the kernels clamp to N).  Two launches, no host sync.
+ * fill : indices [3, E] in coalesced order (ascending graph, sink, source).  E = edge_off[B] read back.
+ * GCM_EUNSUPPORTED unless gcm_spatial_supported(): P <= GCM_SPATIAL_MAX_COLS, (P + 1) * N * 4 bytes of one
+ * graph's positions and row counts fit GCM_SPATIAL_MAX_LDS, N <= 4096 for kNN (candidates held in registers). */
+#define GCM_SPATIAL_RADIUS_CAUSAL 0
+#define GCM_SPATIAL_RADIUS_ALL 1
+#define GCM_SPATIAL_KNN 2
+#define GCM_SPATIAL_MAX_COLS 32
+#define GCM_SPATIAL_MAX_LDS (160 * 1024)
+int gcm_spatial_supported(int mode, int B, int N, int F, int P);
+int gcm_spatial_count(const float* nodes, const int64_t* T, const int64_t* taus, const int32_t* cols, int P,
+                      int mode, float radius, int k, int32_t* row_off, uint64_t* kth, int64_t* edge_off, int B,
+                      int N, int F, gcm_stream_t stream);
+int gcm_spatial_fill(const float* nodes, const int64_t* T, const int64_t* taus, const int32_t* cols, int P,
+                     int mode, float radius, const int32_t* row_off, const uint64_t* kth, const int64_t* edge_off,
+                     int64_t* indices, int64_t E, int B, int N, int F, gcm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
