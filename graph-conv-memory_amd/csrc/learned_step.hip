@@ -14,22 +14,9 @@
 //   k_learned_roll_logits / _pick / _l2   the forward of a whole rollout from empty graphs in three launches
 //                      (DenseGCM.rollout), the edge network per 32-row block with a candidate row.
 //   k_bptt_rows<.., 2> (rows_bptt.hip) + k_learned_bptt_sel + k_learned_bptt_mlp   the time-parallel backward of
-//                      a chain of steps (see "TIME-PARALLEL backward" below): what every fused chain runs.
-//   k_learned_step_bwd backward of ONE step (round 2's sequential form, kept behind gcm_learned_step_bwd for the
-//                      C ABI's single-step callers), everything in one launch:
-//     * GNN adjoint on the live rows (rows j with adj[cur, j] != 0, and cur: gcm.py:314 keeps one
-//       row of the last layer) -> parameter-gradient slab;
-//     * the gradient w.r.t. the ADJACENCY, which is what trains the edge network.  Its chain through
-//       time is dense in the reference (a [B,N,N] tensor per step); here it is carried in compact
-//       time is a dense [B,N,N] tensor PER STEP in the reference (every step's node receives and
-//       returns one); here ONE chain buffer GA [B,N,N] lives across the steps and is updated
-//       sparsely: a step adds dAgg1[l] . x[k] to the rows layer 1 aggregated into (the live rows),
-//       reads row cur - the only entries differentiated at this step,
-//           g_sel_t[j] = dagg2_t . h1_t[j] + GA[cur_t][j]      (j < cur_t),
-//       and undoes the state advance (zero row cur; on overflow, gcm.py:323-355, one shift of the
-//       buffer) for the step before;
-//     * selection adjoint (softmax; both straight-through estimators are identities);
-//     * edge-network adjoint with the forward recomputed in LDS (nothing but `soft` is saved).
+//                      a chain of steps (see "TIME-PARALLEL backward" below): what every fused chain runs.  The
+//                      gradient w.r.t. the ADJACENCY is what trains the edge network; it is followed through the
+//                      recorded steps instead of a dense [B,N,N] tensor per step as in the reference.
 //
 // Shapes: N <= 128, F <= 32, H1 <= 32, H2 <= 32 (BASELINE cfg5: 128 / 32 / 32 / 32).
 #include "fused_common.h"
@@ -195,44 +182,9 @@ __device__ __forceinline__ void relu_ln_rows(float* sP, int tid, int F, const fl
   else relu_ln_rows_t<false>(sP, tid, F, sg, sb, eps, mu_out, rs_out, write);
 }
 
-// LayerNorm + ReLU adjoint of the rows of sP (pre-activation values, overwritten by the gradient w.r.t.
-// them): gx[f] = the gradient w.r.t. the normalised value times gamma; two threads per row as above.
-template <bool FULL, typename GX>
-__device__ __forceinline__ void relu_ln_rows_bwd_t(float* sP, int tid, int F, const float* sMu, const float* sRs,
-                                                   GX gx_of) {
-  const int row = tid >> 1, f0 = (tid & 1) * (FP / 2);
-  const float mean = sMu[row], rstd = sRs[row];
-  float xh[FP / 2], gx[FP / 2], m1 = 0.f, m2 = 0.f;
-#pragma unroll
-  for (int k = 0; k < FP / 2; ++k) {
-    const int f = f0 + k;
-    const float v = sP[row * FS + f];
-    xh[k] = (FULL || f < F) ? ((v > 0.f ? v : 0.f) - mean) * rstd : 0.f;
-    gx[k] = (FULL || f < F) ? gx_of(row, f) : 0.f;
-    m1 += gx[k];
-    m2 = fmaf(gx[k], xh[k], m2);
-  }
-  m1 += gcm_lane_xor1(m1);
-  m2 += gcm_lane_xor1(m2);
-  m1 /= (float)F;
-  m2 /= (float)F;
-#pragma unroll
-  for (int k = 0; k < FP / 2; ++k) {
-    const int f = f0 + k;
-    const float v = sP[row * FS + f];
-    const float da = rstd * (gx[k] - m1 - xh[k] * m2);
-    sP[row * FS + f] = ((FULL || f < F) && v > 0.f) ? da : 0.f;
-  }
-}
-template <typename GX>
-__device__ __forceinline__ void relu_ln_rows_bwd(float* sP, int tid, int F, const float* sMu, const float* sRs,
-                                                 GX gx_of) {
-  if (F == FP) relu_ln_rows_bwd_t<true>(sP, tid, F, sMu, sRs, gx_of);
-  else relu_ln_rows_bwd_t<false>(sP, tid, F, sMu, sRs, gx_of);
-}
-// the same adjoint with the incoming gradient of this thread's 16 columns handed over in registers (gx[k]: the
-// gradient w.r.t. the normalised value times gamma, column f0 + k) and the pre-activations read ONCE: a third of
-// the LDS reads of the form above (the block-granular backward is bound by the instructions it issues)
+// LayerNorm + ReLU adjoint of the rows of sP (pre-activation values, read ONCE and overwritten by the gradient
+// w.r.t. them), two threads per row as above: gxv[k] = the gradient w.r.t. the normalised value times gamma of
+// column f0 + k, handed over in registers (the block-granular backward is bound by the instructions it issues)
 template <bool FULL>
 __device__ __forceinline__ void relu_ln_rows_bwd_v(float* sP, int tid, int F, const float* sMu, const float* sRs,
                                                    const float (&gxv)[FP / 2]) {
@@ -260,24 +212,6 @@ __device__ __forceinline__ void relu_ln_rows_bwd_v(float* sP, int tid, int F, co
     const float da = rstd * (gx[k] - m1 - xh[k] * m2);
     sP[row * FS + f] = ((FULL || f < F) && ((pos >> k) & 1u)) ? da : 0.f;
   }
-}
-
-// c0[o] = b0[o] + W0a[o, :] . x_cur: both vectors in registers before the first use (a load -> fma loop
-// exposed up to F memory round trips on the 32 threads that run it), summed in ascending f
-__device__ __forceinline__ float c0_dot(const float* __restrict__ w_row, const float* __restrict__ xcur,
-                                        float b0, int F) {
-  float wv[FP], xv[FP];
-#pragma unroll
-  for (int f = 0; f < FP; ++f) {
-    wv[f] = w_row[f < F ? f : F - 1];
-    xv[f] = xcur[f < F ? f : F - 1];
-  }
-  asm volatile("" ::: "memory");
-  float c0 = b0;
-#pragma unroll
-  for (int f = 0; f < FP; ++f)
-    if (f < F) c0 = fmaf(wv[f], xv[f], c0);
-  return c0;
 }
 
 __device__ __forceinline__ float wave_max(float v) { return gcm_wave_max(v); }
@@ -1696,7 +1630,7 @@ __global__ __launch_bounds__(64 * RL_WAVES) void k_learned_roll_logits(const flo
       if (lh == 0) sX[32 * FS + li] = li < F ? xc : 0.f;
     }
     wsync();
-    if (lh == 0) {   // c0[o] = b0[o] + W0a[o, :] . x_cur, ascending f (c0_dot's order)
+    if (lh == 0) {   // c0[o] = b0[o] + W0a[o, :] . x_cur, ascending f
       float c0 = sVec[li];
       const float* w = sW0a + li * FS;
       const float* x = sX + 32 * FS;
@@ -1904,462 +1838,8 @@ __global__ __launch_bounds__(256) void k_learned_roll_l2(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward of one step (see the header comment)
-// ---------------------------------------------------------------------------------------------
-// slab per graph (floats): GNN part as the packed GNN vector (dW_rel1 | dW_root1 | db1 | dW_rel2 |
-// dW_root2 | db2), then the edge network as its packed vector.
-__global__ __launch_bounds__(256) void k_learned_step_bwd(
-    const float* __restrict__ g_mx, const float* __restrict__ nodes, const float* __restrict__ adj,
-    const int64_t* __restrict__ cur_idx, const int64_t* __restrict__ count_in,
-    const float* __restrict__ gnn, int act1, int act2, const float* __restrict__ mx,
-    const float* __restrict__ h1, const float* __restrict__ agg1, const float* __restrict__ agg2,
-    const float* __restrict__ soft, const float* __restrict__ mlp, float eps0, float eps1,
-    float* __restrict__ GA, float* __restrict__ slabs, int accumulate, int N, int F,
-    int H1, int H2) {
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 31, lh = lane >> 5;
-  int64_t c64 = cur_idx[b];
-  const int cur = c64 < 0 ? 0 : (c64 > N - 1 ? N - 1 : (int)c64);
-  const bool wrapped = count_in[b] + 1 > N;
-  const Mlp M = unpack_mlp(mlp, F);
-  const int Pg = 2 * H1 * F + H1 + 2 * H2 * H1 + H2, Pm = 3 * F * F + 7 * F + 1;
-  const float* w_rel1 = gnn;
-  const float* w_rel2 = gnn + 2 * H1 * F + H1;
-  const float* w_root2 = w_rel2 + H2 * H1;
-  const float* xg = nodes + (size_t)b * N * F;
-  const float* ag = adj + (size_t)b * N * N;
-  const float* h1g = h1 + (size_t)b * N * H1;
-  const float* a1g = agg1 + (size_t)b * N * F;
-  float* GAg = GA + (size_t)b * N * N;   // this graph's chain buffer (see the header comment)
-  float* slab_g = slabs + (size_t)b * (Pg + Pm);
-
-  extern __shared__ float smem[];
-  float* sX = smem;                    // [NP][FS]
-  float* sP0 = sX + NP * FS;           // P0 -> gP0
-  float* sH0 = sP0 + NP * FS;          // H0
-  float* sP1 = sH0 + NP * FS;          // P1 -> gP1
-  float* sG = sP1 + NP * FS;           // h1 image (phase A), then gH0
-  float* sW0b = sG + NP * FS;          // [o][f]
-  float* sW1 = sW0b + FP * FS;         // [o][f]
-  float* sWr1 = sW1 + FP * FS;         // w_rel1 [h][f]
-  float* sR = sWr1 + FP * FS;          // [4][1024] cross-wave reduction of the dW tiles
-  float* sVec = sR + 4096;             // c0 | b1 | g0 | be0 | g1 | be1 | w2
-  float* sMu0 = sVec + 7 * FP;         // per-row LayerNorm statistics [NP] x 4
-  float* sRs0 = sMu0 + NP;
-  float* sMu1 = sRs0 + NP;
-  float* sRs1 = sMu1 + NP;
-  float* sGl = sRs1 + NP;              // g_logit [NP]
-  float* sSel = sGl + NP;              // g_sel [NP]
-  float* sCoef = sSel + NP;            // adj[cur, :] [NP]
-  float* sD2 = sCoef + NP;             // d2 [32] | u [64] | v [64] | (32 spare) | colsum scratch [256]
-  float* sU = sD2 + 32;
-  float* sVv = sU + 64;
-  float* sCs = sVv + 64 + 32;
-  int* sLive = reinterpret_cast<int*>(sCs + 256);   // [NP] + count
-  // The parameter-gradient slab of this graph is built in LDS and written once: every update below is
-  // a read-modify-write, and against HBM each of the dozen update sites exposed a memory round trip.
-  float* slab = reinterpret_cast<float*>(sLive + NP + 8);   // [Pg + Pm]
-  float* sl_m = slab + Pg;
-
-  LSTAMP(0);
-  // ---- loads: node matrix, h1, weights, row cur of the adjacency, the kept row's vectors, the slab so
-  // far - every global load in flight before the first LDS store (one round trip, not one per matrix) ---
-  {
-    using gcm_fused::Stage;
-    Stage<NP, FP, false, false> st_x, st_h;
-    Stage<FP, FP, false, false> st_w0, st_w1, st_wr;
-    st_x.load(xg, N, F, F, tid);
-    st_h.load(h1g, N, H1, H1, tid);
-    st_w0.load(M.w0 + F, F, F, 2 * F, tid);
-    st_w1.load(M.w1, F, F, F, tid);
-    st_wr.load(w_rel1, H1, F, F, tid);
-    constexpr int SLAB_PER = (2 * FP * FP + FP + 2 * FP * FP + FP + 3 * FP * FP + 7 * FP + 1 + 255) / 256;
-    float sv[SLAB_PER];
-    if (accumulate) {   // (uniform)
-#pragma unroll
-      for (int i = 0; i < SLAB_PER; ++i) {
-        const int e = tid + 256 * i;
-        sv[i] = slab_g[e < Pg + Pm ? e : Pg + Pm - 1];
-      }
-    }
-    asm volatile("" ::: "memory");
-    st_x.store(sX, FS, tid);
-    st_h.store(sG, FS, tid);
-    st_w0.store(sW0b, FS, tid);
-    st_w1.store(sW1, FS, tid);
-    st_wr.store(sWr1, FS, tid);
-#pragma unroll
-    for (int i = 0; i < SLAB_PER; ++i) {
-      const int e = tid + 256 * i;
-      if (e < Pg + Pm) slab[e] = accumulate ? sv[i] : 0.f;
-    }
-  }
-  if (tid < NP) sCoef[tid] = tid < N ? ag[cur * N + tid] : 0.f;
-  if (tid < FP) {
-    const int o = tid < F ? tid : F - 1;
-    const float c0 = c0_dot(M.w0 + (size_t)o * 2 * F, xg + (size_t)cur * F, M.b0[o], F);
-    const bool ok = tid < F;
-    sVec[tid] = ok ? c0 : 0.f;
-    sVec[FP + tid] = ok ? M.b1[o] : 0.f;
-    sVec[2 * FP + tid] = ok ? M.g0[o] : 0.f;
-    sVec[3 * FP + tid] = ok ? M.be0[o] : 0.f;
-    sVec[4 * FP + tid] = ok ? M.g1[o] : 0.f;
-    sVec[5 * FP + tid] = ok ? M.be1[o] : 0.f;
-    sVec[6 * FP + tid] = ok ? M.w2[o] : 0.f;
-    const int oc = tid < H2 ? tid : H2 - 1;
-    const float gm = g_mx[(size_t)b * H2 + oc], y = mx[(size_t)b * H2 + oc];
-    sD2[tid] = tid < H2 ? gm * gcm_act_grad(y, act2) : 0.f;
-  }
-  if (tid < 64) {   // v = agg2 | h1[cur]
-    const int k = tid < 32 ? tid : tid - 32;
-    const int kc = k < H1 ? k : H1 - 1;
-    const float t = tid < 32 ? agg2[(size_t)b * H1 + kc] : h1g[cur * H1 + kc];
-    sVv[tid] = k < H1 ? t : 0.f;
-  }
-  LSTAMP(1);
-  __syncthreads();
-  // ---- phase A: layer-2 adjoint ----------------------------------------------------------------------
-  if (tid < 64) {   // u[m] = sum_o W2c[o][m] d2[o]   (m < 32: dagg2, else dh1cur)
-    const int k = tid < 32 ? tid : tid - 32;
-    const float* wc = (tid < 32 ? w_rel2 : w_root2) + (k < H1 ? k : H1 - 1);
-    float s = 0.f;
-    for (int o = 0; o < H2; ++o) s = fmaf(wc[o * H1], sD2[o], s);
-    sU[tid] = k < H1 ? s : 0.f;
-  }
-  {   // dW2c[o][k] (+)= d2[o] v[k]; db2
-    float* sl_rel2 = slab + 2 * H1 * F + H1;
-    float* sl_root2 = sl_rel2 + H2 * H1;
-    float* sl_b2 = sl_root2 + H2 * H1;
-    for (int e = tid; e < 32 * 64; e += 256) {
-      const int o = e >> 6, k = e & 63, kk = k & 31;
-      if (o < H2 && kk < H1) {
-        float* d = (k < 32 ? sl_rel2 : sl_root2) + o * H1 + kk;
-        *d = (accumulate ? *d : 0.f) + sD2[o] * sVv[k];
-      }
-    }
-    if (tid < H2) sl_b2[tid] = (accumulate ? sl_b2[tid] : 0.f) + sD2[tid];
-  }
-  LSTAMP(2);
-  // live rows: ballot over row cur (entries of the sampled row), list in LDS
-  {
-    const bool pred = tid < N && tid < NP && (sCoef[tid & (NP - 1)] != 0.f || tid == cur);
-    const unsigned long long bal = __ballot(pred);
-    if (lane == 0 && wave < 2) sLive[NP + wave] = __popcll(bal);
-    __syncthreads();
-    const int pos = (wave ? sLive[NP] : 0) + __popcll(bal & ((1ull << lane) - 1ull));
-    if (pred) sLive[pos] = tid;
-  }
-  __syncthreads();
-  const int L = sLive[NP] + sLive[NP + 1];
-  // G1[l][h] = (coef dagg2[h] + [j == cur] dh1cur[h]) act1'(h1[j][h]) -> sR[l][h]  (L <= 128 rows x 32)
-  for (int e = tid; e < L * 32; e += 256) {
-    const int l = e >> 5, h = e & 31, j = sLive[l];
-    const float y = sG[j * FS + h];
-    const float d = sCoef[j] * sU[h] + (j == cur ? sU[32 + h] : 0.f);
-    sR[l * 32 + h] = h < H1 ? d * gcm_act_grad(y, act1) : 0.f;
-  }
-  __syncthreads();
-  LSTAMP(3);
-  {   // layer-1 parameter gradients on the live rows: dW1c[h][m] (+)= sum_l G1[l][h] [agg1 | x][j_l][m]
-    const int h = tid >> 3, m0 = (tid & 7) * 8;
-    float acc[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-    float bsum = 0.f;
-    for (int l = 0; l < L; ++l) {
-      const int j = sLive[l];
-      const float g = sR[l * 32 + h];
-      bsum += g;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int m = m0 + q, f = m & 31;
-        const float a = f < F ? (m < 32 ? a1g[j * F + f] : sX[j * FS + f]) : 0.f;
-        acc[q] = fmaf(g, a, acc[q]);
-      }
-    }
-    if (h < H1) {
-      float* sl_rel1 = slab;
-      float* sl_root1 = slab + H1 * F;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int m = m0 + q, f = m & 31;
-        if (f < F) {
-          float* d = (m < 32 ? sl_rel1 : sl_root1) + h * F + f;
-          *d = (accumulate ? *d : 0.f) + acc[q];
-        }
-      }
-      if ((tid & 7) == 0) {
-        float* d = slab + 2 * H1 * F + h;
-        *d = (accumulate ? *d : 0.f) + bsum;
-      }
-    }
-  }
-  LSTAMP(4);
-  // dAgg1[l][f] = G1[l] . w_rel1[:, f] -> sP0 [l][FS] (free until the edge network is recomputed)
-  for (int e = tid; e < L * 32; e += 256) {
-    const int l = e >> 5, f = e & 31;
-    float s = 0.f;
-    if (f < F) {
-#pragma unroll
-      for (int h = 0; h < 32; ++h) s = fmaf(sR[l * 32 + h], sWr1[h * FS + f], s);
-    }
-    sP0[l * FS + f] = s;
-  }
-  __syncthreads();
-  // the adjacency gradient of the rows layer 1 aggregated into: GA[j_l][k] += dAgg1[l] . x[k] for every
-  // column k (entry (j_l, k) exists from the step that wrote row j_l until node k is dropped: the
-  // chain buffer is rolled with the state below, so later contributions land on the right entries).
-  // Row cur is consumed right here (g_sel) and is not written back.
-  int l_cur = -1;
-  for (int l = 0; l < L; ++l) l_cur = sLive[l] == cur ? l : l_cur;   // (row cur is always in the list)
-  for (int e = tid; e < L * N; e += 256) {
-    const int l = e / N, k = e - l * N, j = sLive[l];
-    if (j != cur) {
-      float s = 0.f;
-#pragma unroll
-      for (int f = 0; f < 32; ++f) s = fmaf(sP0[l * FS + f], sX[k * FS + f], s);
-      GAg[j * N + k] += s;
-    }
-  }
-  LSTAMP(5);
-  // ---- g_sel[j] = dagg2 . h1[j] + GA[cur][j] + dAgg1[cur] . x[j]  (j < cur); selection adjoint ------
-  if (tid < NP) {
-    float s = 0.f;
-    if (tid < cur) {
-      s = GAg[cur * N + tid];
-#pragma unroll
-      for (int h = 0; h < 32; ++h) s = fmaf(sU[h], sG[tid * FS + h], s);
-#pragma unroll
-      for (int f = 0; f < 32; ++f) s = fmaf(sP0[l_cur * FS + f], sX[tid * FS + f], s);
-    }
-    sSel[tid] = s;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    float p[2], g[2], dot = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int j = lane + 64 * c;
-      const bool live = j < cur;
-      p[c] = live ? soft[(size_t)b * N + j] : 0.f;
-      g[c] = live ? sSel[j] : 0.f;
-      dot = fmaf(p[c], g[c], dot);
-    }
-    dot = wave_sum(dot);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) sGl[lane + 64 * c] = p[c] * (g[c] - dot);
-  }
-  LSTAMP(6);
-  // ---- the chain buffer for the previous step: undo the state advance (gcm.py:262-278, 323-355).
-  // No overflow: row cur did not exist before (zero).  Overflow: every entry moves back by one row
-  // and one column, the dropped node's row / column and the new node's row carry nothing.
-  {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();   // every GA read / write above is done
-    if (wrapped) {
-      constexpr int PERG = NP * NP / 256;
-      float gv[PERG];
-#pragma unroll
-      for (int i = 0; i < PERG; ++i) {
-        const int e = tid + 256 * i, r = e / NP, c = e % NP;      // destination entry (r, c) <- (r-1, c-1)
-        const int rs = r - 1, cs = c - 1;
-        const bool ok = r < N && c < N && rs >= 0 && cs >= 0 && rs != cur;
-        const float t = GAg[(rs >= 0 && rs < N ? rs : 0) * N + (cs >= 0 && cs < N ? cs : 0)];
-        gv[i] = ok ? t : 0.f;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < PERG; ++i) {
-        const int e = tid + 256 * i, r = e / NP, c = e % NP;
-        if (r < N && c < N) GAg[r * N + c] = gv[i];
-      }
-    } else if (tid < N) {
-      GAg[cur * N + tid] = 0.f;
-    }
-  }
-  __syncthreads();
-  LSTAMP(7);
-  // ---- edge network: forward recomputed, then its adjoint -------------------------------------------
-  {
-    const f32x16 acc = gemm_rows(sX, sW0b, wave, li, lh);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * wave + gcm_fused::acc_row(r, lh);
-      const float v = acc[r] + sVec[li];
-      sP0[row * FS + li] = v;
-      sH0[row * FS + li] = v;
-    }
-  }
-  __syncthreads();
-  relu_ln_rows(sH0, tid, F, sVec + 2 * FP, sVec + 3 * FP, eps0, sMu0, sRs0);
-  __syncthreads();
-  {
-    const f32x16 acc = gemm_rows(sH0, sW1, wave, li, lh);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sP1[(32 * wave + gcm_fused::acc_row(r, lh)) * FS + li] = acc[r] + sVec[FP + li];
-  }
-  __syncthreads();
-  // statistics of layer 1 (the normalised values are rebuilt where needed)
-  relu_ln_rows(sP1, tid, F, nullptr, nullptr, eps1, sMu1, sRs1, /*write=*/false);
-  __syncthreads();
-  LSTAMP(8);
-  // column sums over the rows (8 row groups x 32 columns): dw2, dgamma1, dbeta1, db2
-  {
-    const int f = tid & 31, grp = tid >> 5;
-    float s_w2 = 0.f, s_g1 = 0.f, s_b1 = 0.f, s_bb = 0.f;
-    const float w2f = sVec[6 * FP + f], g1f = sVec[4 * FP + f], be1f = sVec[5 * FP + f];
-    for (int j = grp; j < N; j += 8) {
-      const float gl = sGl[j];
-      const float v = sP1[j * FS + f];
-      const float xh = ((v > 0.f ? v : 0.f) - sMu1[j]) * sRs1[j];
-      s_w2 = fmaf(gl, fmaf(xh, g1f, be1f), s_w2);   // dw2[f] += gl * H1m[j][f]
-      s_g1 = fmaf(gl * w2f, xh, s_g1);
-      s_b1 = fmaf(gl, w2f, s_b1);
-      s_bb += gl;
-    }
-    auto colsum = [&](float v) {
-      sCs[tid] = v;
-      __syncthreads();
-      float t = 0.f;
-      if (tid < 32) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t += sCs[q * 32 + tid];
-      }
-      __syncthreads();
-      return t;
-    };
-    const int o_w1 = 2 * F * F + 3 * F, o_b1 = o_w1 + F * F, o_g1 = o_b1 + F, o_be1 = o_g1 + F;
-    const int o_w2 = o_be1 + F, o_b2 = o_w2 + F;
-    const float t_w2 = colsum(s_w2), t_g1 = colsum(s_g1), t_b1 = colsum(s_b1), t_bb = colsum(s_bb);
-    if (tid < F) {
-      sl_m[o_w2 + tid] = (accumulate ? sl_m[o_w2 + tid] : 0.f) + t_w2;
-      sl_m[o_g1 + tid] = (accumulate ? sl_m[o_g1 + tid] : 0.f) + t_g1;
-      sl_m[o_be1 + tid] = (accumulate ? sl_m[o_be1 + tid] : 0.f) + t_b1;
-    }
-    if (tid == 0) sl_m[o_b2] = (accumulate ? sl_m[o_b2] : 0.f) + t_bb;
-  }
-  LSTAMP(9);
-  // LayerNorm-1 + ReLU adjoint, row by row: gP1 in place of P1
-  relu_ln_rows_bwd(sP1, tid, F, sMu1, sRs1,
-                   [&](int j, int f) { return sGl[j] * sVec[6 * FP + f] * sVec[4 * FP + f]; });
-  __syncthreads();
-  LSTAMP(10);
-  // db1' = column sums of gP1; dW1 = gP1^T H0 (K = rows, split over the waves); gH0 = gP1 W1
-  const int o_b0 = 2 * F * F, o_g0 = o_b0 + F, o_be0 = o_g0 + F, o_w1 = o_be0 + F, o_b1 = o_w1 + F * F;
-  {
-    const int f = tid & 31, grp = tid >> 5;
-    float s = 0.f;
-    for (int j = grp; j < N; j += 8) s += sP1[j * FS + f];
-    sCs[tid] = s;
-  }
-  {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-    // A(i = o, k = row) = gP1[row][o];  B(k = row, j = f) = H0[row][f]
-    mma32(a, sP1 + 32 * wave * FS, 1, FS, sH0 + 32 * wave * FS, FS, 1, 32, li, lh);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sR[wave * 1024 + gcm_fused::acc_row(r, lh) * 32 + li] = a[r];
-  }
-  __syncthreads();
-  if (tid < F) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t += sCs[q * 32 + tid];
-    sl_m[o_b1 + tid] = (accumulate ? sl_m[o_b1 + tid] : 0.f) + t;
-  }
-  for (int e = tid; e < 1024; e += 256) {
-    const int o = e >> 5, f = e & 31;
-    if (o < F && f < F) {
-      float* d = sl_m + o_w1 + o * F + f;
-      *d = (accumulate ? *d : 0.f) + ((sR[e] + sR[1024 + e]) + (sR[2048 + e] + sR[3072 + e]));
-    }
-  }
-  {   // gH0[rows] = gP1[rows] @ W1  (B(k = o, j = f) = W1[o][f]) -> sG
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    mma32(acc, sP1 + 32 * wave * FS, FS, 1, sW1, FS, 1, 32, li, lh);
-    __syncthreads();   // sR / sCs reads above are done before they are reused; sG (h1) is free
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sG[(32 * wave + gcm_fused::acc_row(r, lh)) * FS + li] = acc[r];
-  }
-  __syncthreads();
-  LSTAMP(11);
-  // dgamma0 / dbeta0 (column sums of gH0 * xhat0, gH0), then LayerNorm-0 + ReLU adjoint: gP0 in place
-  {
-    const int f = tid & 31, grp = tid >> 5;
-    float s_g = 0.f, s_b = 0.f;
-    for (int j = grp; j < N; j += 8) {
-      const float v = sP0[j * FS + f];
-      const float xh = ((v > 0.f ? v : 0.f) - sMu0[j]) * sRs0[j];
-      const float gh = sG[j * FS + f];
-      s_g = fmaf(gh, xh, s_g);
-      s_b += gh;
-    }
-    sCs[tid] = s_g;
-    __syncthreads();
-    if (tid < F) {
-      float t = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += sCs[q * 32 + tid];
-      sl_m[o_g0 + tid] = (accumulate ? sl_m[o_g0 + tid] : 0.f) + t;
-    }
-    __syncthreads();
-    sCs[tid] = s_b;
-    __syncthreads();
-    if (tid < F) {
-      float t = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += sCs[q * 32 + tid];
-      sl_m[o_be0 + tid] = (accumulate ? sl_m[o_be0 + tid] : 0.f) + t;
-    }
-  }
-  relu_ln_rows_bwd(sP0, tid, F, sMu0, sRs0, [&](int j, int f) { return sG[j * FS + f] * sVec[2 * FP + f]; });
-  __syncthreads();
-  LSTAMP(12);
-  // db0 = column sums of gP0; dW0a = db0 (x) x[cur]; dW0b = gP0^T X
-  {
-    const int f = tid & 31, grp = tid >> 5;
-    float s = 0.f;
-    for (int j = grp; j < N; j += 8) s += sP0[j * FS + f];
-    sCs[tid] = s;
-  }
-  {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-    mma32(a, sP0 + 32 * wave * FS, 1, FS, sX + 32 * wave * FS, FS, 1, 32, li, lh);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sR[wave * 1024 + gcm_fused::acc_row(r, lh) * 32 + li] = a[r];
-  }
-  __syncthreads();
-  if (tid < FP) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t += sCs[q * 32 + tid];
-    sVec[tid] = t;   // db0 (c0 is no longer needed)
-    if (tid < F) sl_m[o_b0 + tid] = (accumulate ? sl_m[o_b0 + tid] : 0.f) + t;
-  }
-  __syncthreads();
-  for (int e = tid; e < 1024; e += 256) {
-    const int o = e >> 5, f = e & 31;
-    if (o < F && f < F) {
-      float* da = sl_m + o * 2 * F + f;          // W0a half
-      float* db = sl_m + o * 2 * F + F + f;      // W0b half
-      *da = (accumulate ? *da : 0.f) + sVec[o] * sX[cur * FS + f];
-      *db = (accumulate ? *db : 0.f) + ((sR[e] + sR[1024 + e]) + (sR[2048 + e] + sR[3072 + e]));
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < Pg + Pm; e += 256) slab_g[e] = slab[e];
-  LSTAMP(13);
-}
-
-// ---------------------------------------------------------------------------------------------
-// TIME-PARALLEL backward of a whole chain of steps (round 3; k_learned_step_bwd above is one step at a
-// time, one workgroup per CU, ~20 barrier phases behind a sequential [B,N,N] chain buffer).
+// TIME-PARALLEL backward of a whole chain of steps (round 3; round 2's backward was one step at a time, one
+// workgroup per CU, ~20 barrier phases behind a sequential [B,N,N] chain buffer).
 //
 // With observations that carry no gradient the only path between steps is the adjacency: the entries
 // (j, k) written when node j was inserted are read by layer 1 of every later step in which row j is
@@ -3558,10 +3038,6 @@ __global__ __launch_bounds__(64 * M16_WAVES) void k_learned_bptt_mlp16(BpttB a, 
 constexpr size_t lds_select() { return sizeof(float) * (3 * NP * FS + 2 * FP * FS + FP * GS + 7 * FP + NP); }
 constexpr size_t lds_select_tail() { return lds_select() + sizeof(float) * (NP * FS + 4 * FP * GS); }
 constexpr size_t lds_select_steady() { return lds_select_tail() + sizeof(uint32_t) * (NP * 4 + 4); }
-constexpr size_t lds_bwd() {
-  return sizeof(float) * (5 * NP * FS + 3 * FP * FS + 4096 + 7 * FP + 7 * NP + 32 + 64 + 64 + 32 + 256 + NP + 8 +
-                          (2 * FP * FP + FP + 2 * FP * FP + FP) + (3 * FP * FP + 7 * FP + 1) + 3);
-}
 
 }  // namespace gcm_learned
 
@@ -3801,25 +3277,6 @@ extern "C" int gcm_learned_rollout_fwd(const float* obs, const float* noise, int
   if (rc) return rc;
   hipLaunchKernelGGL(gcm_learned::k_learned_roll_l2, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,
                      (hipStream_t)stream, params, act2, has_bias, H1, H2, R, cache_h1, mx_all, flags, B, T, N, F);
-  return gcm_launch_status();
-}
-
-extern "C" int gcm_learned_step_bwd(const float* g_mx, const float* nodes, const float* adj,
-                                    const int64_t* cur_idx, const int64_t* count_in,
-                                    const float* gnn_params, int act1, int act2, const float* mx,
-                                    const float* h1, const float* agg1, const float* agg2,
-                                    const float* soft, const float* mlp_params, float eps0, float eps1,
-                                    float* GA, float* slabs, int accumulate, int B, int N, int F, int H1,
-                                    int H2, gcm_stream_t stream) {
-  GCM_REQUIRE(g_mx && nodes && adj && cur_idx && count_in && gnn_params && mx && h1 && agg1 && agg2 && soft &&
-              mlp_params && GA && slabs && B > 0);
-  if (!gcm_learned_step_supported(N, F, H1, H2)) return GCM_EUNSUPPORTED;
-  constexpr size_t lds = gcm_learned::lds_bwd();
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  gcm_allow_dynamic_lds((const void*)gcm_learned::k_learned_step_bwd, lds);
-  hipLaunchKernelGGL(gcm_learned::k_learned_step_bwd, dim3(B), dim3(256), lds, (hipStream_t)stream, g_mx,
-                     nodes, adj, cur_idx, count_in, gnn_params, act1, act2, mx, h1, agg1, agg2, soft,
-                     mlp_params, eps0, eps1, GA, slabs, accumulate, N, F, H1, H2);
   return gcm_launch_status();
 }
 

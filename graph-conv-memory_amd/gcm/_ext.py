@@ -1,10 +1,7 @@
-"""Loader / builder of the C++ autograd node of the fused step (csrc/torch_ext/step_ext.cpp).
-
-The node is host plumbing around the same C-ABI calls the Python autograd Function makes
-(gcm_dense_step_fwd / gcm_dense_step_bwd in libgcm_hip.so); it exists because the per-step loop of
-the reference's callers is host-bound.  Built in-tree by `python __graft_entry__.py`
-(`build()` below); when the built module is absent the Python Function in _ops.py is used - the
-same kernels, more interpreter time per step."""
+"""Loader / builder of the C++ host path (csrc/torch_ext/step_ext.cpp): the autograd nodes and host loops of
+the per-step DenseGCM / SparseGCM calls, around the C-ABI calls into libgcm_hip.so.  It exists because the
+per-step loop of the reference's callers is host-bound.  Built in-tree by `python __graft_entry__.py`
+(`build()` below) and required: there is no Python twin of its nodes."""
 import importlib.util
 import os
 
@@ -17,7 +14,6 @@ _SRC = os.path.join(os.path.dirname(_HERE), "csrc", "torch_ext", "step_ext.cpp")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
 
 _mod = None
-_tried = False
 
 
 def build(verbose=False):
@@ -27,7 +23,7 @@ def build(verbose=False):
     from . import _hip
     _hip.lib()   # libgcm_hip.so must exist (and is then already mapped when the module loads)
     os.makedirs(_EXT_DIR, exist_ok=True)
-    global _mod, _tried
+    global _mod
     _mod = cpp_extension.load(
         name=_NAME, sources=[_SRC],
         # host C++ only; the ROCm include path is for c10/hip (current stream / device of the
@@ -39,21 +35,20 @@ def build(verbose=False):
                        f"-L{os.path.join(os.path.dirname(torch.__file__), 'lib')}", "-lc10_hip",
                        "-ltorch_python"],
         build_directory=_EXT_DIR, verbose=verbose)
-    _tried = True
     return _mod
 
 
 def module():
-    """The built extension module, or None when it has not been built."""
-    global _mod, _tried
-    if _mod is None and not _tried:
-        _tried = True
-        if os.environ.get("GCM_NO_TORCH_EXT") != "1" and os.path.exists(_SO):
-            import torch  # noqa: F401  (libtorch must be loaded first)
-            from . import _hip
-            _hip.lib()
-            spec = importlib.util.spec_from_file_location(_NAME, _SO)
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-            _mod = mod
+    """The built extension module; raises _hip.HipLibraryError when it has not been built."""
+    global _mod
+    if _mod is None:
+        import torch  # noqa: F401  (libtorch must be loaded first)
+        from . import _hip
+        if not os.path.exists(_SO):
+            raise _hip.HipLibraryError(f"{_SO} not found: build it with `python __graft_entry__.py`")
+        _hip.lib()
+        spec = importlib.util.spec_from_file_location(_NAME, _SO)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _mod = mod
     return _mod

@@ -27,7 +27,7 @@ STEP_FOUR_WAVES = 256     # gcm_dense_rows_step_colcache: the four-wave kernel w
 SPATIAL_RADIUS_CAUSAL, SPATIAL_RADIUS_ALL, SPATIAL_KNN = 0, 1, 2   # gcm_spatial_count / _fill modes
 SPATIAL_MAX_COLS = 32
 
-ABI_VERSION = 6           # include/gcm_hip.h: GCM_ABI_VERSION
+ABI_VERSION = 7           # include/gcm_hip.h: GCM_ABI_VERSION
 
 _P, _I, _F, _Z, _L = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t,
                      ctypes.c_int64)
@@ -149,7 +149,6 @@ PROTOTYPES = {
     "gcm_learned_mlp_param_count": (_Z, [_I]),
     "gcm_learned_select_fused": (_I, [_P, _P, _P, _P, _I, _P, _F, _F, _F, _P, _I, _I, _I, _P]),
     "gcm_learned_advance_select_fused": (_I, [_P] * 5 + [_I, _P, _F, _F, _F] + [_P] * 6 + [_I, _I, _I, _P]),
-    "gcm_learned_step_bwd": (_I, [_P] * 6 + [_I, _I] + [_P] * 6 + [_F, _F, _P, _P, _I] + [_I] * 5 + [_P]),
     "gcm_dense_rows_bptt_slabs": (_I, [_I, _I]),
     "gcm_learned_step_layout": (_I, [_I] * 6 + [_P]),
     "gcm_dense_rollout_tp_supported": (_I, [_P, _I, _I, _I, _I, _I, _I, _I]),

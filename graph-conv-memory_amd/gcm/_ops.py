@@ -12,37 +12,8 @@ from . import _ext, _hip
 _f32 = torch.float32
 
 
-class KernelTimer:
-    """Optional per-launch timing with HIP events on the launch stream (bench.py uses it
-    for the roofline figures).  Disabled (None) in normal operation: zero overhead."""
-
-    def __init__(self):
-        self.spans = {}
-
-    def launch(self, name, fn, *args):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        rc = fn(*args)
-        b.record()
-        self.spans.setdefault(name, []).append((a, b))
-        return rc
-
-    def summary(self):
-        """name -> (launches, mean ms).  Call after a device synchronize."""
-        out = {}
-        for name, spans in self.spans.items():
-            ms = [a.elapsed_time(b) for a, b in spans]
-            out[name] = (len(ms), sum(ms) / len(ms))
-        return out
-
-
-TIMER = None
-
-
 def _call(name, *args):
-    fn = getattr(_hip.lib(), name)
-    rc = TIMER.launch(name, fn, *args) if TIMER is not None else fn(*args)
-    _hip.check(rc, name)
+    _hip.check(getattr(_hip.lib(), name)(*args), name)
 
 
 def _empty_like(t):
@@ -676,9 +647,6 @@ class StepConfig:
         self.ws_bytes = 0
         self.ws = None
         self.device = device
-        self._layouts = {}
-        self.fn_fwd = lib.gcm_dense_step_fwd
-        self.fn_bwd = lib.gcm_dense_step_bwd
         self.has_distance = any(d.kind == _hip.SEL_DISTANCE for d in descs)
         self._cpp, self._cpp_handle, self._cpp_call = None, None, None
         # the live-row step (rows_step.hip): index-writing selectors (<= 16 hops in all) and at most
@@ -688,8 +656,7 @@ class StepConfig:
             all(d.kind in (_hip.SEL_TEMPORAL, _hip.SEL_DENSE, _hip.SEL_DISTANCE) for d in descs)
             and n_dist <= 1 and not any(d.kind == _hip.SEL_DISTANCE and d.bidirectional for d in descs)
             and sum(d.n_hops for d in descs if d.kind == _hip.SEL_TEMPORAL) <= 16
-            and lib.gcm_dense_rows_supported(N, F, H1, H2)
-            and _ext.module() is not None and hasattr(_ext.module(), "RowsFast"))
+            and lib.gcm_dense_rows_supported(N, F, H1, H2))
         self._rows_fast = None
         # ... and its form that also differentiates w.r.t. the observations / the incoming nodes
         self.dx_ok = bool(self.rows_ok and lib.gcm_dense_rows_dx_supported(N, F, H1, H2))
@@ -712,38 +679,16 @@ class StepConfig:
         self.P_total = self.P + self.Pm
         self.eps = (float(mods[2].eps), float(mods[5].eps))
         self.cutoff = 1.0 / (1 + sel.num_edge_samples)
-        self._zero_chain, self._zero_params = {}, {}
         self.rows_ok = False
 
     def learned_cpp_handle(self):
-        """address of the C++ twin of the learned-step config (0 when the extension lacks it)"""
+        """address of the C++ twin of the learned-step config"""
         h = getattr(self, "_learned_cpp_h", None)
         if h is None:
-            ext = _ext.module()
-            if ext is None or not hasattr(ext, "LearnedCfg") or TIMER is not None:
-                h = 0
-            else:
-                self._learned_cpp = ext.LearnedCfg(self.N, self.F, self.H1, self.H2, self.acts[0], self.acts[1],
-                                                   self.has_bias, self.eps[0], self.eps[1], self.cutoff)
-                h = self._learned_cpp.handle()
-            self._learned_cpp_h = h
+            self._learned_cpp = _ext.module().LearnedCfg(self.N, self.F, self.H1, self.H2, self.acts[0], self.acts[1],
+                                                         self.has_bias, self.eps[0], self.eps[1], self.cutoff)
+            h = self._learned_cpp_h = self._learned_cpp.handle()
         return h
-
-    def zero_chain(self, B, dev):
-        """the proxy whose GRADIENT is the adjacency-gradient chain buffer: a [B,N,N] view of one
-        zero (no memory)"""
-        z = self._zero_chain.get(dev)
-        if z is None:
-            z = torch.zeros(1, 1, 1, device=dev)
-            self._zero_chain[dev] = z
-        return z.expand(B, self.N, self.N)       # a fresh view object per call (it gets a grad_fn)
-
-    def zero_params(self, dev):
-        z = self._zero_params.get(dev)
-        if z is None:
-            z = torch.zeros(self.P_total, device=dev)
-            self._zero_params[dev] = z
-        return z
 
     _learned_fast = None
 
@@ -790,27 +735,20 @@ class StepConfig:
         return f
 
     def cpp_handle(self):
-        """address of the C++ twin of this config (0 when the torch extension is not built)"""
+        """address of the C++ twin of this config"""
         h = self._cpp_handle
         if h is None:
-            ext = _ext.module()
-            if ext is None:
-                h = 0
-            else:
-                self._cpp = ext.StepCfg(self.arr_ptr, self.n_desc, self.acts[0], self.acts[1],
-                                        self.has_bias, self.N, self.F, self.H1, self.H2)
-                h = self._cpp.handle()
-            self._cpp_handle = h
+            self._cpp = _ext.module().StepCfg(self.arr_ptr, self.n_desc, self.acts[0], self.acts[1],
+                                              self.has_bias, self.N, self.F, self.H1, self.H2)
+            h = self._cpp_handle = self._cpp.handle()
         return h
 
     def cpp_call(self):
-        """(ext.fused_step, config handle, device index) or None when the extension is not built"""
+        """(ext.fused_step, config handle, device index): the C++ node of the per-step fused step"""
         c = self._cpp_call
         if c is None:
-            h = self.cpp_handle()
-            c = (_ext.module().fused_step, h, self.device.index) if h else False
-            self._cpp_call = c
-        return c or None
+            c = self._cpp_call = (_ext.module().fused_step, self.cpp_handle(), self.device.index)
+        return c
 
     def refresh_pointers(self):
         """re-read the device pointers baked into the selector descriptors (a re-assigned
@@ -839,26 +777,6 @@ class StepConfig:
             self.ws_bytes = need
         return (self.ws.data_ptr() if self.ws is not None else None), self.ws_bytes
 
-    def layout(self, B, need_bwd):
-        """(total floats, float offsets of nodes|adj|mx|h1|agg1|agg2, bwd layout) for a batch size"""
-        key = (B, need_bwd)
-        lay = self._layouts.get(key)
-        if lay is None:
-            N, F, H1, H2, P = self.N, self.F, self.H1, self.H2, self.P
-            n_nodes, n_adj, n_mx = _pad64(B * N * F), _pad64(B * N * N), _pad64(B * H2)
-            n_h1, n_agg2 = _pad64(B * N * H1), _pad64(B * H1)
-            o_adj = n_nodes
-            o_mx = o_adj + n_adj
-            o_h1 = o_mx + n_mx
-            o_agg1 = o_h1 + n_h1
-            o_agg2 = o_agg1 + n_nodes
-            total = (o_agg2 + n_agg2) if need_bwd else o_h1
-            n_obs, n_p = _pad64(B * F), _pad64(P)
-            bwd = (n_nodes + n_obs + n_p + B * P, n_nodes, n_nodes + n_obs, n_nodes + n_obs + n_p)
-            lay = (total, o_adj, o_mx, o_h1, o_agg1, o_agg2, bwd)
-            self._layouts[key] = lay
-        return lay
-
     def unpack_ptrs(self, packed):
         """device pointers (w_rel1, b1, w_root1, w_rel2, b2, w_root2) into the packed vector"""
         F, H1, H2 = self.F, self.H1, self.H2
@@ -871,86 +789,6 @@ class StepConfig:
         b2 = w_root2 + 4 * H2 * H1
         return (w_rel1, b1 if self.has_bias & 1 else None, w_root1,
                 w_rel2, b2 if self.has_bias & 2 else None, w_root2)
-
-
-def _pad64(n):
-    return (n + 63) & ~63
-
-
-class _FusedStep(torch.autograd.Function):
-    """One DenseGCM step as ONE autograd node and ONE C call per direction
-    (gcm_dense_step_fwd / gcm_dense_step_bwd): (obs, nodes_in, packed params) ->
-    (mx, nodes_out, adj_out, cur, count_out).  Outputs and the activations saved for backward
-    live in one allocation.  (This is the per-step hot loop of the host: no helper layers.)"""
-
-    @staticmethod
-    def forward(ctx, obs, nodes_in, packed, adj_in, count_in, flags, cfg):
-        if not (obs.is_contiguous() and nodes_in.is_contiguous() and adj_in.is_contiguous()):
-            obs, nodes_in, adj_in = obs.contiguous(), nodes_in.contiguous(), adj_in.contiguous()
-        B = obs.shape[0]
-        N, F, H2 = cfg.N, cfg.F, cfg.H2
-        need = ctx.needs_input_grad
-        need_bwd = need[0] or need[1] or need[2]
-        total, o_adj, o_mx, o_h1, o_agg1, o_agg2, _ = cfg.layout(B, need_bwd)
-        buf = torch.empty(total, device=obs.device, dtype=_f32)
-        ibuf = torch.empty(2, B, device=obs.device, dtype=torch.int64)
-        base = buf.data_ptr()
-        ib = ibuf.data_ptr()
-        if need_bwd:
-            p_h1, p_agg1, p_agg2 = base + 4 * o_h1, base + 4 * o_agg1, base + 4 * o_agg2
-        else:
-            p_h1 = p_agg1 = p_agg2 = None
-        ws_ptr, ws_bytes = cfg.workspace(B)
-        args = (obs.data_ptr(), nodes_in.data_ptr(), adj_in.data_ptr(), count_in.data_ptr(), base,
-                base + 4 * o_adj, ib, ib + 8 * B, cfg.arr_ptr, cfg.n_desc, packed.data_ptr(),
-                cfg.has_bias, cfg.acts[0], cfg.acts[1], base + 4 * o_mx, p_h1, p_agg1, p_agg2,
-                flags.data_ptr(), ws_ptr, ws_bytes, B, N, F, cfg.H1, H2,
-                torch.cuda.current_stream().cuda_stream)
-        rc = TIMER.launch("gcm_dense_step_fwd", cfg.fn_fwd, *args) if TIMER is not None \
-            else cfg.fn_fwd(*args)
-        if rc:
-            _hip.check(rc, "gcm_dense_step_fwd")
-        nodes_out = buf[:B * N * F].view(B, N, F)
-        adj_out = buf[o_adj:o_adj + B * N * N].view(B, N, N)
-        mx = buf[o_mx:o_mx + B * H2].view(B, H2)
-        cur, count_out = ibuf[0], ibuf[1]
-        ctx.save_for_backward(buf, ibuf, count_in, packed)
-        ctx.cfg, ctx.B = cfg, B
-        ctx.mark_non_differentiable(adj_out, cur, count_out)
-        ctx.set_materialize_grads(False)   # backward handles None: no zero-fill launches
-        return mx, nodes_out, adj_out, cur, count_out
-
-    @staticmethod
-    def backward(ctx, g_mx, g_nodes_out, _ga, _gc, _gn):
-        buf, ibuf, count_in, packed = ctx.saved_tensors
-        cfg, B = ctx.cfg, ctx.B
-        N, F, H2, P = cfg.N, cfg.F, cfg.H2, cfg.P
-        _, o_adj, o_mx, o_h1, o_agg1, o_agg2, (tot_b, o_obs, o_par, o_ws) = cfg.layout(B, True)
-        if g_mx is None:
-            g_mx = torch.zeros(B, H2, device=buf.device)
-        elif not g_mx.is_contiguous():
-            g_mx = g_mx.contiguous()
-        if g_nodes_out is None:
-            g_no = None
-        else:
-            g_no = (g_nodes_out if g_nodes_out.is_contiguous() else g_nodes_out.contiguous()).data_ptr()
-        out = torch.empty(tot_b, device=buf.device, dtype=_f32)
-        ob = out.data_ptr()
-        base = buf.data_ptr()
-        args = (g_mx.data_ptr(), g_no, base, base + 4 * o_adj, ibuf.data_ptr(), count_in.data_ptr(),
-                packed.data_ptr(), cfg.has_bias, cfg.acts[0], cfg.acts[1], base + 4 * o_mx,
-                base + 4 * o_h1, base + 4 * o_agg1, base + 4 * o_agg2, ob, ob + 4 * o_obs,
-                ob + 4 * o_par, ob + 4 * o_ws, 4 * B * P, B, N, F, cfg.H1, H2,
-                torch.cuda.current_stream().cuda_stream)
-        rc = TIMER.launch("gcm_dense_step_bwd", cfg.fn_bwd, *args) if TIMER is not None \
-            else cfg.fn_bwd(*args)
-        if rc:
-            _hip.check(rc, "gcm_dense_step_bwd")
-        need = ctx.needs_input_grad
-        g_nodes_in = out[:B * N * F].view(B, N, F) if need[1] else None
-        g_obs = out[o_obs:o_obs + B * F].view(B, F) if need[0] else None
-        g_params = out[o_par:o_par + P] if need[2] else None
-        return g_obs, g_nodes_in, g_params, None, None, None, None
 
 
 class SlabHolder:
@@ -999,22 +837,6 @@ class _ParamGate(torch.autograd.Function):
 
 def param_gate(packed, holder):
     return _ParamGate.apply(packed, holder)
-
-
-def fused_step(obs, nodes_in, packed, adj_in, count_in, flags, cfg, slab_acc=None, is_head=True):
-    """The per-step node: the C++ autograd node when gcm/_lib/ext is built (same C-ABI calls,
-    no interpreter on the path), else the Python Function above.  Kernel timing (TIMER) goes
-    through the Python one, whose launches it can bracket.
-    slab_acc [B, P]: where the C++ node's backward accumulates the parameter-gradient slabs (summed
-    once by _ParamGate); is_head: first step of a chain of hidden states.
-    -> (mx, nodes_out, adj_out, cur, count_out)"""
-    if TIMER is None:
-        handle = cfg.cpp_handle()
-        if handle:
-            return _ext.module().fused_step(obs, nodes_in, packed, adj_in, count_in, flags, handle,
-                                            torch._C._cuda_getCurrentRawStream(obs.device.index),
-                                            slab_acc, is_head)
-    return _FusedStep.apply(obs, nodes_in, packed, adj_in, count_in, flags, cfg)
 
 
 # Time-parallel BPTT keeps T*B*(N*F + F + P) floats of scratch; above this many bytes the
@@ -1125,86 +947,6 @@ class _FusedRollout(torch.autograd.Function):
         need = ctx.needs_input_grad
         return (g_obs if need[0] else None, g_nodes0 if need[1] else None,
                 flat if need[2] else None, None, None, None, None)
-
-
-class _LearnedStep(torch.autograd.Function):
-    """One DenseGCM + LearnedEdge step (default edge network, observations without gradient) as ONE
-    autograd node: state advance, fused edge network + gumbel selection, dense 2-layer GNN forward;
-    ONE kernel backward (gcm_learned_step_bwd).  The adjacency's gradient chain through time travels
-    as the gradient of the `dchain` proxy (ONE [B,N,N] buffer, updated sparsely: csrc/learned_step.hip), the
-    parameter gradients accumulate into the gate's slab array.
-    inputs: packed = GNN vector | edge-network vector (gated), dchain_in; the rest is data."""
-
-    @staticmethod
-    def forward(ctx, packed, dchain_in, obs, nodes_in, adj_in, count_in, noise, noise_is_exp, flags, cfg,
-                slab_acc, is_head):
-        lib = _hip.lib()
-        B, N, F, H1, H2, P = obs.shape[0], cfg.N, cfg.F, cfg.H1, cfg.H2, cfg.P
-        dev = obs.device
-        st = _hip.stream()
-        obs, nodes_in, adj_in = obs.contiguous(), nodes_in.contiguous(), adj_in.contiguous()
-        noise = noise.contiguous()
-        _hip.on_device(obs, nodes_in, adj_in, count_in, noise, packed, flags)
-        need_bwd = ctx.needs_input_grad[0]
-        nodes_out, adj_out = torch.empty_like(nodes_in), torch.empty_like(adj_in)
-        ibuf = torch.empty(2, B, dtype=torch.int64, device=dev)
-        cur, count_out = ibuf[0], ibuf[1]
-        p = _hip.ptr
-        _call("gcm_state_advance_fwd", p(nodes_in), p(adj_in), None, p(count_in), p(obs), p(nodes_out),
-              p(adj_out), None, p(cur), p(count_out), p(flags), B, N, F, st)
-        soft = torch.empty(B, N, device=dev, dtype=_f32)
-        base = packed.data_ptr()
-        _call("gcm_learned_select_fused", p(nodes_out), p(adj_out), p(cur), p(noise), int(noise_is_exp),
-              base + 4 * P, cfg.eps[0], cfg.eps[1], cfg.cutoff, p(soft), B, N, F, st)
-        mx = torch.empty(B, H2, device=dev, dtype=_f32)
-        h1 = torch.empty(B, N, H1, device=dev, dtype=_f32) if need_bwd else None
-        agg1 = torch.empty(B, N, F, device=dev, dtype=_f32) if need_bwd else None
-        agg2 = torch.empty(B, H1, device=dev, dtype=_f32) if need_bwd else None
-        w = cfg.unpack_ptrs(packed)
-        _call("gcm_dense_gnn2_row_fwd", p(nodes_out), p(adj_out), p(cur), w[0], w[1], w[2], cfg.acts[0],
-              w[3], w[4], w[5], cfg.acts[1], p(mx), p(h1), p(agg1), p(agg2), p(flags), B, N, F, H1, H2, st)
-        if need_bwd:
-            ctx.save_for_backward(packed, nodes_out, adj_out, ibuf, count_in, mx, h1, agg1, agg2, soft)
-            ctx.cfg, ctx.slab_acc, ctx.is_head = cfg, slab_acc, is_head
-        dchain_out = cfg.zero_chain(B, dev)
-        ctx.mark_non_differentiable(nodes_out, adj_out, cur, count_out)
-        ctx.set_materialize_grads(False)
-        return mx, dchain_out, nodes_out, adj_out, cur, count_out
-
-    @staticmethod
-    def backward(ctx, g_mx, g_chain, _gn, _ga, _gc, _gk):
-        packed, nodes_out, adj_out, ibuf, count_in, mx, h1, agg1, agg2, soft = ctx.saved_tensors
-        cfg = ctx.cfg
-        B, N, F, H1, H2, P = mx.shape[0], cfg.N, cfg.F, cfg.H1, cfg.H2, cfg.P
-        dev = mx.device
-        if g_mx is None and g_chain is None:
-            return (None,) * 12
-        if g_mx is None:
-            g_mx = torch.zeros(B, H2, device=dev, dtype=_f32)
-        g_mx = g_mx.contiguous()
-        # the chain buffer: handed down from the step after this one (mutated in place), or new
-        D = g_chain if (g_chain is not None and g_chain.is_contiguous()) else \
-            (torch.zeros(B, N, N, device=dev, dtype=_f32) if g_chain is None else g_chain.contiguous())
-        p = _hip.ptr
-        base = packed.data_ptr()
-        _call("gcm_learned_step_bwd", p(g_mx), p(nodes_out), p(adj_out), ibuf.data_ptr(), p(count_in), base,
-              cfg.acts[0], cfg.acts[1], p(mx), p(h1), p(agg1), p(agg2), p(soft), base + 4 * P, cfg.eps[0],
-              cfg.eps[1], p(D), p(ctx.slab_acc), 1, B, N, F, H1, H2, _hip.stream())
-        g_packed = cfg.zero_params(dev) if ctx.is_head else None     # a defined gradient: the gate runs
-        return (g_packed, D if ctx.needs_input_grad[1] else None) + (None,) * 10
-
-
-def learned_step(packed, dchain_in, obs, nodes_in, adj_in, count_in, noise, noise_is_exp, flags, cfg,
-                 slab_acc, is_head):
-    """The per-step node of DenseGCM + LearnedEdge: the C++ autograd node when gcm/_lib/ext is built (same
-    C-ABI calls, no interpreter on the path), else the Python Function above."""
-    h = cfg.learned_cpp_handle()
-    if h:
-        return _ext.module().learned_step(packed, dchain_in, obs, nodes_in, adj_in, count_in, noise,
-                                          int(noise_is_exp), flags, h,
-                                          torch._C._cuda_getCurrentRawStream(obs.device.index), slab_acc, is_head)
-    return _LearnedStep.apply(packed, dchain_in, obs, nodes_in, adj_in, count_in, noise, noise_is_exp, flags,
-                              cfg, slab_acc, is_head)
 
 
 def fused_rollout(obs, nodes0, packed, adj0, num_nodes0, flags, cfg):

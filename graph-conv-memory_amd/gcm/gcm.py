@@ -133,9 +133,6 @@ class DenseGCM(torch.nn.Module):
         self._ctr = [0]       # steps since the last poll (a list: nn.Module.__setattr__ is slow)
         self._fast = None     # (RowsFast, flag word) of the last live-row step: what __call__ tries first
         self._learned_chain = None   # (packed vector, LearnedChain, grad mode): the fused LearnedEdge steps' one autograd node
-        # False: the round-2 backward of the fused LearnedEdge step (one kernel per step behind a [B,N,N]
-        # gradient chain buffer) instead of the time-parallel one - kept for A/B tests
-        self.learned_time_parallel = True
         # fused LearnedEdge steps: how many steps' gumbel draws one RNG launch makes (B x N x 4 bytes each)
         self.noise_pool_steps = 64
         # False: no cached steps (the first N steps of a LearnedEdge rollout from empty graphs on a donated state as
@@ -568,9 +565,9 @@ class DenseGCM(torch.nn.Module):
             Fe = cfg.F
             sizes = sizes + (2 * Fe * Fe, Fe, Fe, Fe, Fe * Fe, Fe, Fe, Fe, Fe, 1)
         dev = tensors[0].device
-        ext = _ops._ext.module()
-        if fold is None and ext is not None and hasattr(ext, "pack_params") and all(t is not None for t in tensors):
-            packed = ext.pack_params(list(tensors))     # (one autograd node: every parameter's gradient a view)
+        if fold is None and all(t is not None for t in tensors):
+            # (one autograd node: every parameter's gradient a view)
+            packed = _ops._ext.module().pack_params(list(tensors))
         else:
             parts = [t.reshape(-1) if t is not None else torch.zeros(n, device=dev)
                      for t, n in zip(tensors, sizes)]
@@ -583,7 +580,7 @@ class DenseGCM(torch.nn.Module):
         if packed.requires_grad:
             packed.register_hook(lambda g: used.__setitem__(0, True))
         # (the gate of the per-step fused nodes - _gate() - is made when one of them first asks for it)
-        gate = [None, None, cfg.P_total if cfg.learned_sel is not None else cfg.P, dev]
+        gate = [None, None, cfg.P, dev]
         for d in cfg.descs:               # a re-assigned dist_param must not leave a stale pointer
             if d.kind == _hip.SEL_DISTANCE:
                 cfg.refresh_pointers()
@@ -687,9 +684,9 @@ class DenseGCM(torch.nn.Module):
         return mx, out
 
     def _forward_learned(self, x, hidden, cfg, flags, link):
-        """DenseGCM + LearnedEdge as fused kernels (csrc/learned_step.hip): 4 launches forward, one
-        backward.  The returned adjacency carries no autograd history of its own: its gradient chain
-        travels with the hidden state in compact form (`_gcm_dchain` on the adjacency tensor)."""
+        """DenseGCM + LearnedEdge as fused kernels (csrc/learned_step.hip), one time-parallel backward per chain.
+        The returned adjacency carries no autograd history of its own: it carries the index of the step that
+        wrote it (`_gcm_lin`), which the chain's backward follows."""
         nodes, adj, weights, num_nodes = hidden
         root = self._packed_params(cfg, head=link is None)
         B = x.shape[0]
@@ -709,57 +706,41 @@ class DenseGCM(torch.nn.Module):
             noise, is_exp = pool[0][pool[1]], 1
             pool[1] += 1
         ext = _ops._ext.module()
-        if self.learned_time_parallel and ext is not None and hasattr(ext, "learned_step2") and _ops.TIMER is None:
-            # every step of a chain of hidden states hangs its belief tensor on ONE autograd node
-            # (LearnedChainNode in csrc/torch_ext/step_ext.cpp); the adjacency carries the index of the step
-            # that wrote it, so that the time-parallel backward can follow the chain (or tree) of states
-            lc = self._learned_chain
-            # (a chain that starts from the empty graphs of hidden = None runs its first N steps as cached steps,
-            #  LearnedChain in step_ext.cpp: its caches belong to ONE such rollout)
-            fresh = getattr(nodes, "_gcm_fresh", False)
-            if fresh:
-                nodes._gcm_fresh = False      # (a donated state is this very tensor at every later step)
-            fresh = fresh and self.learned_cached_steps
-            if (lc is None or lc[0] is not root or lc[1].executed() or lc[2] != torch.is_grad_enabled()
-                    or (fresh and lc[1].total_steps() > 0)):
-                lc = self._learned_chain = (root, ext.LearnedChain(cfg.learned_cpp_handle(), root,
-                                                                   bool(self.donate_state)),
-                                            torch.is_grad_enabled())
-            lin = getattr(adj, "_gcm_lin", None)
-            parent = lin[1] if (lin is not None and lin[0] is lc[1]) else -1
-            mx, n2, a2, cur, c2, idx = ext.learned_step2(lc[1], x, nodes, adj, num_nodes, noise, is_exp, flags, parent,
-                                                         bool(fresh))
-            if idx >= 0:
-                a2._gcm_lin = (lc[1], idx)
-            # the next call of this chain may skip the interpreter: DenseGCM.__call__ -> LearnedFast.step (C++)
-            if (sel.noise_fn is None and not self.mutate_num_nodes_on_overflow and hasattr(ext, "LearnedFast")
-                    and self.learned_fast_path):
-                lf = cfg.learned_fast(self)
-                lf.arm(lc[1], self._noise_pool, self._token, weakref.ref(cfg), flags, root, weights, idx, B, x.shape[1],
-                       cfg.N)
-                every = {"deferred": self.poll_interval, "sync": 1, "off": float("inf")}[self.finite_check]
-                self._fast = (lf.step, flags, every)
-            if lc[1].donates():      # the state was advanced in place: the caller's own tuple
-                n2._gcm_link = (self._token, a2, cfg, flags, None, root, x.shape, weights, c2)
-                if self.mutate_num_nodes_on_overflow:
-                    raise NotImplementedError("mutate_num_nodes_on_overflow with donate_state")
-                if self.finite_check != "off":
-                    self._poll(flags)
-                return mx, hidden
-        elif self._gate()[0] is not None:
-            gated, holder = self._gate()
-            is_head = link is None or link[5] is not root
-            dchain = getattr(adj, "_gcm_dchain", None) if not is_head else None
-            if dchain is None:
-                dchain = cfg.zero_chain(B, x.device)
-            mx, dchain_out, n2, a2, cur, c2 = _ops.learned_step(
-                gated, dchain, x, nodes, adj, num_nodes, noise, is_exp, flags, cfg, holder.get(B), is_head)
-            a2._gcm_dchain = dchain_out
-        else:
-            with torch.no_grad():
-                mx, _, n2, a2, cur, c2 = _ops.learned_step(
-                    root, cfg.zero_chain(B, x.device), x, nodes, adj, num_nodes, noise, is_exp, flags, cfg,
-                    None, True)
+        # every step of a chain of hidden states hangs its belief tensor on ONE autograd node
+        # (LearnedChainNode in csrc/torch_ext/step_ext.cpp); the adjacency carries the index of the step
+        # that wrote it, so that the time-parallel backward can follow the chain (or tree) of states
+        lc = self._learned_chain
+        # (a chain that starts from the empty graphs of hidden = None runs its first N steps as cached steps,
+        #  LearnedChain in step_ext.cpp: its caches belong to ONE such rollout)
+        fresh = getattr(nodes, "_gcm_fresh", False)
+        if fresh:
+            nodes._gcm_fresh = False      # (a donated state is this very tensor at every later step)
+        fresh = fresh and self.learned_cached_steps
+        if (lc is None or lc[0] is not root or lc[1].executed() or lc[2] != torch.is_grad_enabled()
+                or (fresh and lc[1].total_steps() > 0)):
+            lc = self._learned_chain = (root, ext.LearnedChain(cfg.learned_cpp_handle(), root,
+                                                               bool(self.donate_state)),
+                                        torch.is_grad_enabled())
+        lin = getattr(adj, "_gcm_lin", None)
+        parent = lin[1] if (lin is not None and lin[0] is lc[1]) else -1
+        mx, n2, a2, cur, c2, idx = ext.learned_step2(lc[1], x, nodes, adj, num_nodes, noise, is_exp, flags, parent,
+                                                     bool(fresh))
+        if idx >= 0:
+            a2._gcm_lin = (lc[1], idx)
+        # the next call of this chain may skip the interpreter: DenseGCM.__call__ -> LearnedFast.step (C++)
+        if sel.noise_fn is None and not self.mutate_num_nodes_on_overflow and self.learned_fast_path:
+            lf = cfg.learned_fast(self)
+            lf.arm(lc[1], self._noise_pool, self._token, weakref.ref(cfg), flags, root, weights, idx, B, x.shape[1],
+                   cfg.N)
+            every = {"deferred": self.poll_interval, "sync": 1, "off": float("inf")}[self.finite_check]
+            self._fast = (lf.step, flags, every)
+        if lc[1].donates():      # the state was advanced in place: the caller's own tuple
+            n2._gcm_link = (self._token, a2, cfg, flags, None, root, x.shape, weights, c2)
+            if self.mutate_num_nodes_on_overflow:
+                raise NotImplementedError("mutate_num_nodes_on_overflow with donate_state")
+            if self.finite_check != "off":
+                self._poll(flags)
+            return mx, hidden
         n2._gcm_link = (self._token, a2, cfg, flags, None, root, x.shape, weights, c2)
         if self.mutate_num_nodes_on_overflow:
             num_nodes.copy_(cur)
@@ -780,14 +761,10 @@ class DenseGCM(torch.nn.Module):
             packed, slab_acc = gated, holder.get(x.shape[0])
         else:
             is_head, packed, slab_acc = True, root, None
-        fast = cfg.cpp_call() if _ops.TIMER is None else None
-        if fast is not None:      # (function, handle, device index) of the C++ node: no wrapper layers
-            mx, nodes_out, adj_out, cur, num_nodes_next = fast[0](
-                x, nodes, packed, adj, num_nodes, flags, fast[1],
-                torch._C._cuda_getCurrentRawStream(fast[2]), slab_acc, is_head)
-        else:
-            mx, nodes_out, adj_out, cur, num_nodes_next = _ops.fused_step(
-                x, nodes, packed, adj, num_nodes, flags, cfg, slab_acc, is_head)
+        fast = cfg.cpp_call()     # (function, handle, device index) of the C++ node: no wrapper layers
+        mx, nodes_out, adj_out, cur, num_nodes_next = fast[0](
+            x, nodes, packed, adj, num_nodes, flags, fast[1], torch._C._cuda_getCurrentRawStream(fast[2]),
+            slab_acc, is_head)
         nodes_out._gcm_link = (self._token, adj_out, cfg, flags, None, root, x.shape, weights,
                                num_nodes_next)
         if self.mutate_num_nodes_on_overflow:
@@ -842,19 +819,18 @@ class DenseGCM(torch.nn.Module):
             cfg = self._fused_plan(z, obs.new_empty(0, self.graph_size, self.graph_size), obs.new_zeros(0), obs.shape[-1])
             # (T <= N: the adjacency entries a step writes are read by later steps' layer 1 - their gradient reaches
             #  the selection through ONE chain's records, so a rollout is not split at the overflow)
-            if (cfg is not None and cfg.learned_sel is not None and self.learned_time_parallel
-                    and self.learned_cached_steps and obs.shape[0] <= self.graph_size
-                    and not (torch.is_grad_enabled() and obs.requires_grad)):
+            if (cfg is not None and cfg.learned_sel is not None and self.learned_cached_steps
+                    and obs.shape[0] <= self.graph_size and not (torch.is_grad_enabled() and obs.requires_grad)):
                 return self._rollout_learned(obs, cfg)
             # forward temporal hops only, from empty graphs, observations without gradient: no recurrence at all - the
             # whole forward as two launches over every (step, graph) (csrc/rollout_tp.hip), one autograd node
             if (cfg is not None and cfg.learned_sel is None and cfg.fold is None and cfg.rows_ok
                     and self.rollout_time_parallel
                     and not (torch.is_grad_enabled() and obs.requires_grad)):
-                ext = _ops._ext.module()
-                if ext is not None and hasattr(ext, "rows_rollout_tp") and cfg.cpp_handle():
+                if cfg.cpp_handle():
                     flags = self._flag_word(obs.device)
-                    r = ext.rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True), obs, flags)
+                    r = _ops._ext.module().rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True), obs,
+                                                           flags)
                     if r is not None:
                         mx, nodes, adj, count = r
                         if self.finite_check == "sync":
@@ -896,11 +872,10 @@ class DenseGCM(torch.nn.Module):
         autograd node whose backward is the chain's time-parallel one.  The hidden state it returns is a plain
         tensor tuple: like every rollout() it ends its gradient chain (a later call's gradient does not reach this
         rollout's selections - truncated BPTT at the call boundary, which is what RLlib's state passing does)."""
-        ext = _ops._ext.module()
         T, B = obs.shape[0], obs.shape[1]
         N = cfg.N
-        if (ext is None or not hasattr(ext, "learned_rollout") or not cfg.learned_cpp_handle() or (N & 3) or (cfg.F & 3)
-                or B > 65535):            # (gcm_learned_rollout_fwd: GCM_EUNSUPPORTED above 65535 graphs - ADVICE r4)
+        # (gcm_learned_rollout_fwd: GCM_EUNSUPPORTED above 65535 graphs - ADVICE r4)
+        if (N & 3) or (cfg.F & 3) or B > 65535:
             return self._rollout_loop(obs, self.get_initial_hidden_state(obs[0]), True)
         root = self._packed_params(cfg, head=True)
         sel = cfg.learned_sel
@@ -910,7 +885,8 @@ class DenseGCM(torch.nn.Module):
         else:                             # torch.nn.functional.gumbel_softmax draws -log(Exp(1)) the same way
             noise, is_exp = torch.empty(T, B, N, device=obs.device).exponential_(), 1
         flags = self._flag_word(obs.device)
-        mx, nodes, adj, count = ext.learned_rollout(cfg.learned_cpp_handle(), root, obs, noise, is_exp, flags)
+        mx, nodes, adj, count = _ops._ext.module().learned_rollout(cfg.learned_cpp_handle(), root, obs, noise, is_exp,
+                                                                   flags)
         if self.finite_check == "sync":
             self.check_flags()
         elif self.finite_check == "deferred" and not torch.cuda.is_current_stream_capturing():

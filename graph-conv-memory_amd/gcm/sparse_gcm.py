@@ -124,13 +124,10 @@ class SparseGCM(torch.nn.Module):
         plan, the one readback, insert, edges, merge, flatten, CSR, both layers, extract, one autograd node.
         None: the layered path below (any other selector / GNN / option)."""
         if self._fast_plan is None:
-            from . import _ext
             from .sparse_edge_selectors.temporal import TemporalEdge
             plan = False
-            ext = _ext.module()
             g, sel = self.gnn, self.edge_selectors
-            if (ext is not None and hasattr(ext, "sparse_temporal_step") and type(sel) is TemporalEdge
-                    and self.aux_edge_selectors is None and self.preprocessor is None
+            if (type(sel) is TemporalEdge and self.aux_edge_selectors is None and self.preprocessor is None
                     and self.positional_encoder is None and self.max_hops is None
                     and isinstance(g, _nn.Sequential) and len(g.arg_names) == 3):
                 xn = g.arg_names[0]
@@ -153,7 +150,9 @@ class SparseGCM(torch.nn.Module):
                             convs[1].lin_root] + [m for m, _, _ in g.stages()]
                     hooks = [d for m in mods for d in (m._forward_hooks, m._forward_pre_hooks, m._backward_hooks,
                                                        m._backward_pre_hooks)]
-                    plan = (ext.sparse_temporal_step, sel._hops_desc, convs[0], acts[0], convs[1], acts[1], hooks)
+                    from . import _ext
+                    plan = (_ext.module().sparse_temporal_step, sel._hops_desc, convs[0], acts[0], convs[1], acts[1],
+                            hooks)
             self.__dict__["_fast_plan"] = plan
         plan = self._fast_plan
         if plan and any(plan[6]):      # (a hook was registered since)

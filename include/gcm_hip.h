@@ -57,12 +57,13 @@ typedef void* gcm_stream_t; /* hipStream_t */
 
 int gcm_version(void);
 /* ABI revision of this header: bumped whenever an EXISTING entry point's signature or the size of a caller-allocated
- * buffer changes (round 5 did both: the weight image of gcm_dense_rows_cached_weight_image grew from 16 384 to
- * gcm_dense_rows_cached_weight_image_floats() = 36 864 floats, and gcm_edge_distance_step_cached /
- * gcm_learned_step_cached(_functional) / gcm_learned_bptt_cached gained pointer arguments mid-signature).  A binding
+ * buffer changes, or an entry point is removed (6: round 5 did the first two - the weight image of
+ * gcm_dense_rows_cached_weight_image grew from 16 384 to gcm_dense_rows_cached_weight_image_floats() = 36 864 floats,
+ * and gcm_edge_distance_step_cached / gcm_learned_step_cached(_functional) / gcm_learned_bptt_cached gained pointer
+ * arguments mid-signature; 7: gcm_learned_step_bwd, the single-step LearnedEdge backward, was retired).  A binding
  * compares gcm_abi_version() with the GCM_ABI_VERSION it was written against before any other call (gcm/_hip.py
  * does; INTEGRATION.md shows the stub) - stale ctypes prototypes would otherwise shift pointers silently. */
-#define GCM_ABI_VERSION 6
+#define GCM_ABI_VERSION 7
 int gcm_abi_version(void);
 const char* gcm_status_string(int code);
 
@@ -822,22 +823,6 @@ int gcm_learned_advance_select_fused(const float* obs, const float* nodes_in, co
                                      float* nodes_out, float* adj_out, int64_t* cur_out,
                                      int64_t* count_out, float* soft, uint32_t* flags, int B, int N, int F,
                                      gcm_stream_t stream);
-
-/* Backward of one DenseGCM + LearnedEdge step when the observations carry no gradient: GNN adjoint on
- * the live rows, the adjacency gradient in compact form, selection adjoint, edge-network adjoint
- * (forward recomputed).  nodes / adj: the step's OUTPUT state; h1 / agg1 [B,N,.], agg2, mx as saved
- * by gcm_dense_gnn2_row_fwd; soft from gcm_learned_select_fused; count_in = num_nodes before the
- * step.  GA [B,N,N] is the chain buffer of the adjacency gradient: in, as left by the step after this
- * one (zeros for the last step of a chain); out, for the step before (this step's live rows added,
- * row cur consumed, the state advance undone).  slabs
- * [B, gnn2_param_count + mlp_param_count]: per-graph parameter gradients, overwritten or
- * (accumulate != 0) added to; the caller sums them once (gcm_sum_slabs). */
-int gcm_learned_step_bwd(const float* g_mx, const float* nodes, const float* adj,
-                         const int64_t* cur_idx, const int64_t* count_in, const float* gnn_params,
-                         int act1, int act2, const float* mx, const float* h1, const float* agg1,
-                         const float* agg2, const float* soft, const float* mlp_params, float eps0,
-                         float eps1, float* GA, float* slabs, int accumulate, int B, int N, int F,
-                         int H1, int H2, gcm_stream_t stream);
 
 /* ---- time-batched rollout (caller loop ray_gcm.py:200-202) --------- */
 

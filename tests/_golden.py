@@ -119,7 +119,8 @@ def fp64_rollout_bounds(ref, obs, hidden, weight, sel_factory, graph_size, facto
     """The oracle on (obs, hidden) in fp32 and in float64, loss = sum(out * weight): ->
     (out32, final hidden32, {param name: (g64, atol)}, (out64, out_atol)) with
     atol = max(factor x |reference-fp32 - fp64|, floor x scale) - what fp32 can deliver for the case,
-    instead of a fixed rtol.  sel_factory() -> a fresh oracle selector (stateless ones may be shared)."""
+    instead of a fixed rtol.  sel_factory() -> a fresh oracle selector (stateless ones may be shared).
+    obs with requires_grad (a leaf without a gradient yet): the same bound for its gradient, under "obs"."""
     import copy
     from oracle import dense as od
     ref.zero_grad(set_to_none=True)
@@ -129,10 +130,14 @@ def fp64_rollout_bounds(ref, obs, hidden, weight, sel_factory, graph_size, facto
     ref64 = copy.deepcopy(ref).double()
     ref64.zero_grad(set_to_none=True)
     h64 = None if hidden is None else tuple(t.double() if t.is_floating_point() else t.clone() for t in hidden)
-    out64, _ = od.dense_rollout(obs.double(), h64, ref64, graph_size=graph_size, edge_selectors=sel_factory())
+    obs64 = obs.detach().double().requires_grad_(obs.requires_grad)
+    out64, _ = od.dense_rollout(obs64, h64, ref64, graph_size=graph_size, edge_selectors=sel_factory())
     (out64 * weight.double()).sum().backward()
+    pairs = list(zip(ref.named_parameters(), ref64.named_parameters()))
+    if obs.requires_grad:
+        pairs.append((("obs", obs), ("obs", obs64)))
     bounds = {}
-    for (k, p32), (_, p64) in zip(ref.named_parameters(), ref64.named_parameters()):
+    for (k, p32), (_, p64) in pairs:
         scale = float(p64.grad.abs().max())
         err = float((p32.grad.double() - p64.grad).abs().max())
         bounds[k] = (p64.grad, max(factor * err, floor * scale))

@@ -188,31 +188,32 @@ def _loop(mem, obs, hidden=None, detach_at=()):
     return torch.stack(outs), hidden
 
 
-def test_cpp_node_matches_python_node(monkeypatch):
-    """The C++ autograd node and the Python Function make the same C-ABI calls: identical
-    beliefs, state and gradients (bit for bit), overflow included."""
-    from gcm import _ext, _ops
-    if _ext.module() is None:
-        pytest.skip("torch extension not built (python __graft_entry__.py builds it)")
-    obs = torch.rand(40, 3, 32, device=DEV)
-    res = []
-    for use_cpp in (True, False):
-        mem, g = _cfg2_like()
-        mem.rows_dx = False          # the round-1 fused step (one kernel per step and direction), both hosts
-        if not use_cpp:
-            monkeypatch.setattr(_ops.StepConfig, "cpp_handle", lambda self: 0)
-        o = obs.clone().requires_grad_(True)
-        out, hid = _loop(mem, o)
-        (out * torch.linspace(0.5, 1.5, out.numel(), device=DEV).view_as(out)).sum().backward()
-        res.append((out.detach(), hid, o.grad, [p.grad.clone() for p in g.parameters()]))
-    assert torch.equal(res[0][0], res[1][0])
-    for a, b in zip(res[0][1], res[1][1]):
-        assert torch.equal(a, b)
-    assert torch.equal(res[0][2], res[1][2])
-    for a, b in zip(res[0][3], res[1][3]):
-        # C++ node: per-graph slabs accumulate over the steps, one sum at the gate; Python node:
-        # one slab sum per step, the engine adds the T results - same terms, different order
-        torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6 * float(b.abs().max()))
+def test_cpp_fused_node_matches_oracle():
+    """The C++ autograd node of the per-step fused step (FusedStepFn: gcm_dense_step_fwd / gcm_dense_step_bwd, the
+    parameter gradient summed once at the gate) through the overflow, with observations that need a gradient:
+    beliefs, final state, observation and parameter gradients against the oracle (tolerances from its float64
+    evaluation, tests/_golden.py)."""
+    from _golden import fp64_rollout_bounds
+    T, B, N, F = 40, 3, 32, 32
+    mem, g = _cfg2_like(N=N, F=F, H=F)
+    mem.rows_dx = False          # the round-1 fused step (one kernel per step and direction)
+    ref = od.canonical_gnn(F, F)
+    ref.load_state_dict({k: v.cpu() for k, v in g.state_dict().items()})
+    obs = torch.rand(T, B, F)
+    w = torch.linspace(0.5, 1.5, T * B * F).view(T, B, F)
+    o = obs.to(DEV).requires_grad_(True)
+    out, hid = _loop(mem, o)
+    (out * w.to(DEV)).sum().backward()
+    mem.check_flags()
+    assert mem.rows_steps() == 0, "a step left the fused node"
+    out32, hid32, bounds, (out64, out_atol) = fp64_rollout_bounds(
+        ref, obs.clone().requires_grad_(True), None, w, lambda: od.TemporalBackedge([1, 2, 4]), N)
+    assert float((out.detach().cpu().double() - out64).abs().max()) <= out_atol
+    for i in (0, 1, 3):
+        assert torch.equal(hid[i].detach().cpu(), hid32[i]), i
+    for k, grad in [("obs", o.grad)] + [(k, p.grad) for k, p in g.named_parameters()]:
+        g64, atol = bounds[k]
+        assert float((grad.cpu().double() - g64).abs().max()) <= atol, k
 
 
 def test_parameter_gradient_chain_survives_detach_and_restarts():
