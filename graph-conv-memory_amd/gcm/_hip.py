@@ -76,6 +76,13 @@ PROTOTYPES = {
     "gcm_csr_graphconv_fwd": (_I, [_P] * 10 + [_L, _I, _I, _I, _P]),
     "gcm_csr_graphconv_bwd_workspace_bytes": (_Z, [_L, _I, _I]),
     "gcm_csr_graphconv_bwd": (_I, [_P] * 19 + [_Z, _L, _L, _I, _I, _I, _P]),
+    "gcm_dense_gcnconv_fwd": (_I, [_P] * 9 + [_I] * 5 + [_F, _P]),
+    "gcm_dense_gcnconv_bwd_workspace_bytes": (_Z, [_I] * 4),
+    "gcm_dense_gcnconv_bwd": (_I, [_P] * 13 + [_Z] + [_I] * 5 + [_F, _P]),
+    "gcm_gcn_norm": (_I, [_P] * 9 + [_L, _L, _I, _I, _F, _P]),
+    "gcm_csr_gcnconv_fwd": (_I, [_P] * 9 + [_L, _L, _I, _I, _P]),
+    "gcm_csr_gcnconv_bwd_workspace_bytes": (_Z, [_L, _L, _I, _I]),
+    "gcm_csr_gcnconv_bwd": (_I, [_P] * 21 + [_Z, _L, _L, _I, _I, _I, _I, _P]),
     "gcm_learned_pairs_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "gcm_learned_pairs_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "gcm_learned_select_fwd": (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _P]),

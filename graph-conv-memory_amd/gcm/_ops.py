@@ -561,6 +561,126 @@ def csr_graphconv(x, w_edge, w_rel, b_rel, w_root, graph, act=_hip.ACT_NONE):
     return _CsrGraphConv.apply(x, w_edge, w_rel, b_rel, w_root, graph, act)
 
 
+# ---------------------------------------------------------------------------
+# DenseGCNConv / GCNConv (PyG; csrc/gcnconv.hip)
+# ---------------------------------------------------------------------------
+class _DenseGCNConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, adj, w, bias, add_loop, loop_value):
+        x, adj, w = x.contiguous(), adj.contiguous(), w.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, adj, w, bias)
+        B, N, Fi = x.shape
+        Fo = w.shape[0]
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert w.shape == (Fo, Fi)
+        dev = x.device
+        out = torch.empty(B, N, Fo, device=dev, dtype=_f32)
+        y = torch.empty(B, N, Fo, device=dev, dtype=_f32)
+        deg = torch.empty(B, N, device=dev, dtype=_f32)
+        dinv = torch.empty(B, N, device=dev, dtype=_f32)
+        agg = torch.empty(B, N, Fo, device=dev, dtype=_f32) if any(ctx.needs_input_grad) else None
+        _call("gcm_dense_gcnconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(out),
+              _hip.ptr(y), _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), B, N, Fi, Fo, int(add_loop),
+              float(loop_value), _hip.stream())
+        ctx.save_for_backward(x, adj, w, y, agg, deg, dinv)
+        ctx.loop = (int(add_loop), float(loop_value))
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, w, y, agg, deg, dinv = ctx.saved_tensors
+        B, N, Fi = x.shape
+        Fo = w.shape[0]
+        need_x, need_adj, need_w, need_b, _, _ = ctx.needs_input_grad
+        need_b = need_b and ctx.has_bias
+        g_out = g_out.contiguous()
+        dev = x.device
+        lib = _hip.lib()
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_w = torch.empty_like(w) if need_w else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws_bytes = lib.gcm_dense_gcnconv_bwd_workspace_bytes(B, N, Fi, Fo)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_dense_gcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w), _hip.ptr(y),
+              _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_w),
+              _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, ctx.loop[0], ctx.loop[1], _hip.stream())
+        return g_x, g_adj, g_w, g_b, None, None
+
+
+def dense_gcnconv(x, adj, w, bias, add_loop, loop_value):
+    return _DenseGCNConv.apply(x, adj, w, bias, add_loop, loop_value)
+
+
+class _CsrGCNConv(torch.autograd.Function):
+    """x [M,Fi]; w_edge [E] in CSR order or None (unit weights)."""
+
+    @staticmethod
+    def forward(ctx, x, w_edge, w, bias, graph, normalize, add_self_loops, fill):
+        x, w = x.contiguous(), w.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        w_edge = None if w_edge is None else w_edge.contiguous()
+        _hip.on_device(x, w_edge, w, bias)
+        M, Fi = x.shape
+        Fo = w.shape[0]
+        E = graph.E
+        assert M == graph.M
+        dev = x.device
+        dst = graph.dst_csr()
+        coef = torch.empty(E, device=dev, dtype=_f32)
+        dinv = torch.empty(M, device=dev, dtype=_f32)
+        loop_w = torch.empty(M, device=dev, dtype=_f32)
+        loop_coef = torch.empty(M, device=dev, dtype=_f32)
+        loop_e = torch.empty(M, device=dev, dtype=_i64)
+        _call("gcm_gcn_norm", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(w_edge),
+              _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loop_w), _hip.ptr(loop_coef), _hip.ptr(loop_e), M, E,
+              int(normalize), int(add_self_loops), float(fill), _hip.stream())
+        out = torch.empty(M, Fo, device=dev, dtype=_f32)
+        agg = torch.empty(M, Fi, device=dev, dtype=_f32) if any(ctx.needs_input_grad) else None
+        _call("gcm_csr_gcnconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(coef),
+              _hip.ptr(loop_coef), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(agg), M, E, Fi, Fo,
+              _hip.stream())
+        ctx.save_for_backward(x, w_edge, w, agg, dst, coef, dinv, loop_w, loop_coef, loop_e)
+        ctx.graph, ctx.has_bias = graph, bias is not None
+        ctx.norm = (int(normalize), int(add_self_loops))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_edge, w, agg, dst, coef, dinv, loop_w, loop_coef, loop_e = ctx.saved_tensors
+        graph = ctx.graph
+        M, Fi = x.shape
+        Fo = w.shape[0]
+        E = graph.E
+        need_x, need_we, need_w, need_b, _, _, _, _ = ctx.needs_input_grad
+        need_b = need_b and ctx.has_bias
+        need_we = need_we and w_edge is not None
+        g_out = g_out.contiguous()
+        dev = x.device
+        lib = _hip.lib()
+        col_ptr = rows = perm = None
+        if (need_x or need_we) and E > 0:
+            col_ptr, rows, perm = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_we = torch.zeros_like(w_edge) if need_we else None
+        g_w = torch.empty_like(w) if need_w else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws_bytes = lib.gcm_csr_gcnconv_bwd_workspace_bytes(M, E, Fi, Fo)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_csr_gcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(agg), _hip.ptr(graph.row_ptr),
+              _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm),
+              _hip.ptr(w_edge), _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loop_w), _hip.ptr(loop_coef),
+              _hip.ptr(loop_e), _hip.ptr(w), _hip.ptr(g_x), _hip.ptr(g_we), _hip.ptr(g_w), _hip.ptr(g_b),
+              _hip.ptr(ws), ws_bytes, M, E, Fi, Fo, ctx.norm[0], ctx.norm[1], _hip.stream())
+        return g_x, g_we, g_w, g_b, None, None, None, None
+
+
+def csr_gcnconv(x, w_edge, w, bias, graph, normalize, add_self_loops, fill):
+    return _CsrGCNConv.apply(x, w_edge, w, bias, graph, normalize, add_self_loops, fill)
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

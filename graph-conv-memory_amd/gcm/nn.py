@@ -102,6 +102,87 @@ class GraphConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
 
 
+def _glorot_zero(lin, bias):
+    torch.nn.init.xavier_uniform_(lin.weight)
+    if bias is not None:
+        torch.nn.init.zeros_(bias)
+
+
+class DenseGCNConv(torch.nn.Module):
+    """PyG's DenseGCNConv: A = adj with the diagonal set to 1 (2 if improved) when add_loop,
+    d = clamp(rowsum(A), min=1)^-1/2, out = d_i * sum_j A_ij d_j (x W^T)_j + bias; adj [B,N,N] float
+    (adj[b,i,j]: edge j -> i), x [B,N,F].  Forward and backward are HIP kernels (csrc/gcnconv.hip).
+    Parameters `lin.weight`, `bias` as in PyG 2.x; GCNConv loads the same state_dict.  Not a
+    DenseGraphConv: the fused GraphConv paths of Sequential and DenseGCM do not apply to it."""
+
+    def __init__(self, in_channels, out_channels, improved=False, bias=True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.improved = in_channels, out_channels, improved
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot_zero(self.lin, self.bias)
+
+    def forward(self, x, adj, mask=None, add_loop=True):
+        x = x.unsqueeze(0) if x.dim() == 2 else x
+        adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
+        if adj.dtype != torch.float32:
+            raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
+        if adj.shape[0] != x.shape[0]:
+            adj = adj.expand(x.shape[0], -1, -1)
+        out = _ops.dense_gcnconv(x, adj, self.lin.weight, self.bias, add_loop, 2.0 if self.improved else 1.0)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
+class GCNConv(torch.nn.Module):
+    """PyG's GCNConv (flow source_to_target): edge_index [2,E] = (source, sink), x [M,F].  With
+    normalize, gcn_norm: add_remaining_self_loops (fill 2 if improved, else 1; an existing loop keeps
+    its weight), in-degree, deg^-1/2 with inf -> 0; then out = A~ (x W^T) + bias.  The normalisation
+    and the CSR aggregation fused with the linear are HIP kernels (csrc/gcnconv.hip).  Uses the
+    `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed here.  Not a
+    GraphConv: SparseGCM runs a GCN stack through its generic path."""
+
+    def __init__(self, in_channels, out_channels, improved=False, cached=False, add_self_loops=True,
+                 normalize=True, bias=True):
+        super().__init__()
+        if cached:
+            raise NotImplementedError("cached=True is not implemented: every GCM call builds a new graph")
+        self.in_channels, self.out_channels, self.improved = in_channels, out_channels, improved
+        self.cached, self.add_self_loops, self.normalize = cached, add_self_loops, normalize
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot_zero(self.lin, self.bias)
+
+    def forward(self, x, edge_index, edge_weight=None):
+        w = edge_weight
+        if w is not None and w.numel() != edge_index.shape[1]:
+            raise ValueError(f"edge_weight has {w.numel()} entries for {edge_index.shape[1]} edges")
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("GCNConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        if w is not None and getattr(w, "gcm_unit_weights", False):
+            w = None     # unit weights without a gradient: the kernels count 1 per edge
+        if w is not None and graph.csr_perm is not None:
+            w = w[graph.csr_perm]
+        return _ops.csr_gcnconv(x, w, self.lin.weight, self.bias, graph, self.normalize,
+                                self.add_self_loops, 2.0 if self.improved else 1.0)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).

@@ -328,6 +328,56 @@ int gcm_csr_graphconv_bwd(const float* g_out, const float* out, const float* x, 
                           void* workspace, size_t workspace_bytes, int64_t M, int64_t E, int Fi,
                           int Fo, int act, gcm_stream_t stream);
 
+/* ---- GCNConv / DenseGCNConv (PyG; csrc/gcnconv.hip) ---------------------------- */
+
+/* Dense: A = adj with A[b,i,i] := loop_value when add_loop (overwritten, not added);
+ * deg = max(rowsum(A), 1); d = deg^-1/2; out = d_i * sum_j A_ij d_j (x W^T)_j + bias.
+ * x [B,N,Fi], adj [B,N,N] (adj[b,i,j]: edge j -> i), w [Fo,Fi], bias [Fo] or NULL, out [B,N,Fo].
+ * Saved for the backward: y = x W^T [B,N,Fo], deg = rowsum(A) before the clamp [B,N], dinv = d
+ * [B,N] (all three required); agg = sum_j A_ij d_j y_j [B,N,Fo] (NULL without a backward).
+ * Fi, Fo <= 128, any N; GCM_EUNSUPPORTED otherwise. */
+int gcm_dense_gcnconv_fwd(const float* x, const float* adj, const float* w, const float* bias, float* out,
+                          float* y, float* agg, float* deg, float* dinv, int B, int N, int Fi, int Fo,
+                          int add_loop, float loop_value, gcm_stream_t stream);
+
+/* Backward of the above.  Outputs (each may be NULL to skip): g_x [B,N,Fi], g_adj [B,N,N] (the direct
+ * term d_i d_j <g_i, y_j> plus the degree term of row i on every entry; 0 on an overwritten
+ * diagonal), g_w [Fo,Fi], g_bias [Fo] (overwritten, summed over B). */
+size_t gcm_dense_gcnconv_bwd_workspace_bytes(int B, int N, int Fi, int Fo);
+int gcm_dense_gcnconv_bwd(const float* g_out, const float* x, const float* adj, const float* w, const float* y,
+                          const float* agg, const float* deg, const float* dinv, float* g_x, float* g_adj,
+                          float* g_w, float* g_bias, void* workspace, size_t workspace_bytes, int B, int N,
+                          int Fi, int Fo, int add_loop, float loop_value, gcm_stream_t stream);
+
+/* Sparse: PyG's gcn_norm over a destination CSR (row_ptr [M+1], col [E] = sources, dst [E] = the
+ * row of every entry; w [E] in CSR order or NULL = unit weights).  With add_self_loops every i -> i
+ * entry gets coef 0 and node i one loop of weight loop_w[i]: the last such entry's weight (its CSR
+ * position in loop_e[i]), else fill (loop_e[i] = -1).  deg[i] = sum of the counted in-weights,
+ * dinv = deg^-1/2 with 0 where deg == 0; coef[e] = dinv[src] w dinv[dst], loop_coef[i] = dinv^2
+ * loop_w.  normalize == 0: coef = w, no loops, dinv = 1.  Outputs: coef [E], dinv/loop_w/loop_coef
+ * [M], loop_e [M]. */
+int gcm_gcn_norm(const int64_t* row_ptr, const int64_t* col, const int64_t* dst, const float* w, float* coef,
+                 float* dinv, float* loop_w, float* loop_coef, int64_t* loop_e, int64_t M, int64_t E,
+                 int normalize, int add_self_loops, float fill, gcm_stream_t stream);
+
+/* out[i] = (loop_coef[i] x_i + sum_e coef[e] x[col[e]]) W^T + bias.  x [M,Fi], w [Fo,Fi], bias [Fo]
+ * or NULL, out [M,Fo]; agg (NULL without a backward) receives the aggregate [M,Fi]. */
+int gcm_csr_gcnconv_fwd(const float* x, const int64_t* row_ptr, const int64_t* col, const float* coef,
+                        const float* loop_coef, const float* w, const float* bias, float* out, float* agg,
+                        int64_t M, int64_t E, int Fi, int Fo, gcm_stream_t stream);
+
+/* Backward.  col_ptr/rows/perm: the CSC by source as for gcm_csr_graphconv_bwd; w_edge: the CSR-order
+ * weights given to gcm_gcn_norm.  Outputs (NULL to skip): g_x [M,Fi], g_edge [E] (CSR order, through
+ * the coefficients and the degrees), g_w [Fo,Fi], g_bias [Fo]. */
+size_t gcm_csr_gcnconv_bwd_workspace_bytes(int64_t M, int64_t E, int Fi, int Fo);
+int gcm_csr_gcnconv_bwd(const float* g_out, const float* x, const float* agg, const int64_t* row_ptr,
+                        const int64_t* col, const int64_t* dst, const int64_t* col_ptr, const int64_t* rows,
+                        const int64_t* perm, const float* w_edge, const float* coef, const float* dinv,
+                        const float* loop_w, const float* loop_coef, const int64_t* loop_e, const float* w,
+                        float* g_x, float* g_edge, float* g_w, float* g_bias, void* workspace,
+                        size_t workspace_bytes, int64_t M, int64_t E, int Fi, int Fo, int normalize,
+                        int add_self_loops, gcm_stream_t stream);
+
 /* ---- LearnedEdge (src/gcm/edge_selectors/learned.py:53-125) ------------------- */
 
 /* learned.py:66-72: pairs[b, j, :] = cat(nodes[b, cur_b], nodes[b, j]) for j < cur_b, zero rows
