@@ -23,6 +23,7 @@ STEP_TWO_LAUNCH = 32      # ... of the cached step: a distance selector and the 
 STEP_IMG_V4 = 64          # ... its weights as 16-byte loads (the image's second layout)
 BPTT_MANY_ROWS = 128      # gcm_dense_rows_bptt: records with many live rows per graph (DenseEdge)
 STEP_ONE_WAVE = 512       # gcm_dense_rows_step_cached: the one-wave kernel where the two-wave form exists (A/B)
+STEP_NOT_LEAN = 1024      # gcm_dense_rows_step_cached: img4b instead of the lean cached step where that applies (A/B)
 STEP_FOUR_WAVES = 256     # gcm_dense_rows_step_colcache: the four-wave kernel where the eight-wave form exists (A/B)
 SPATIAL_RADIUS_CAUSAL, SPATIAL_RADIUS_ALL, SPATIAL_KNN = 0, 1, 2   # gcm_spatial_count / _fill modes
 SPATIAL_MAX_COLS = 32

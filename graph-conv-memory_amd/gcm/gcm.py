@@ -163,6 +163,10 @@ class DenseGCM(torch.nn.Module):
         # live list) while wave 0 computes - ~120 instructions off a one-wave instruction stream.  False (env
         # GCM_ONE_WAVE=1): the one-wave kernel (A/B)
         self.rows_bookkeeping_wave = os.environ.get("GCM_ONE_WAVE", "0") != "1"
+        # True: that two-wave step at tanh / tanh with at most four forward hops runs in its lean form
+        # (csrc/rows_cached_lean.hip: the step resolved on the host, the arguments its loads need preloaded into SGPRs,
+        # layer 2's weights in flight under layer 1).  False (env GCM_LEAN_STEP=0): k_step_rows_cached_img4b (A/B)
+        self.rows_lean_step = os.environ.get("GCM_LEAN_STEP", "1") == "1"
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
         self.rollout_time_parallel = True
@@ -662,7 +666,8 @@ class DenseGCM(torch.nn.Module):
                 cfg._cpp.set_cached_flags(
                     (0 if (self.rows_one_launch_distance or not cfg.has_distance) else _hip.STEP_TWO_LAUNCH)
                     | (_hip.STEP_IMG_V4 if self.rows_weight_image_v4 else 0)
-                    | (0 if self.rows_bookkeeping_wave else _hip.STEP_ONE_WAVE))
+                    | (0 if self.rows_bookkeeping_wave else _hip.STEP_ONE_WAVE)
+                    | (0 if self.rows_lean_step else _hip.STEP_NOT_LEAN))
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
         mx, n2, a2, c2, donate = fast.run(x, nodes, adj, weights, num_nodes, root, flags, cfg.cpp_handle(),
                                           self.donate_state, need_dx, bool(fresh and self.rows_cached_steps))
