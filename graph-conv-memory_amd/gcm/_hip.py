@@ -84,6 +84,12 @@ PROTOTYPES = {
     "gcm_csr_gcnconv_fwd": (_I, [_P] * 9 + [_L, _L, _I, _I, _P]),
     "gcm_csr_gcnconv_bwd_workspace_bytes": (_Z, [_L, _L, _I, _I]),
     "gcm_csr_gcnconv_bwd": (_I, [_P] * 21 + [_Z, _L, _L, _I, _I, _I, _I, _P]),
+    "gcm_dense_gatconv_fwd": (_I, [_P] * 14 + [_I] * 7 + [_F, _P]),
+    "gcm_dense_gatconv_bwd_workspace_bytes": (_Z, [_I] * 6),
+    "gcm_dense_gatconv_bwd": (_I, [_P] * 17 + [_Z] + [_I] * 6 + [_F, _P]),
+    "gcm_csr_gatconv_fwd": (_I, [_P] * 14 + [_L, _L] + [_I] * 5 + [_F, _P]),
+    "gcm_csr_gatconv_bwd_workspace_bytes": (_Z, [_L, _L] + [_I] * 4),
+    "gcm_csr_gatconv_bwd": (_I, [_P] * 21 + [_Z, _L, _L] + [_I] * 5 + [_F, _P]),
     "gcm_learned_pairs_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "gcm_learned_pairs_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "gcm_learned_select_fwd": (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _P]),

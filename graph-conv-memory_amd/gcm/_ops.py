@@ -681,6 +681,125 @@ def csr_gcnconv(x, w_edge, w, bias, graph, normalize, add_self_loops, fill):
     return _CsrGCNConv.apply(x, w_edge, w, bias, graph, normalize, add_self_loops, fill)
 
 
+# ---------------------------------------------------------------------------
+# DenseGATConv / GATConv (PyG, GAT v1; csrc/gatconv.hip)
+# ---------------------------------------------------------------------------
+class _DenseGATConv(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (only its nonzero pattern is read: no gradient), w [H*C,Fi], att_* [H*C]."""
+
+    @staticmethod
+    def forward(ctx, x, adj, w, att_src, att_dst, bias, heads, concat, add_loop, slope):
+        x, adj, w = x.contiguous(), adj.contiguous(), w.contiguous()
+        att_src, att_dst = att_src.contiguous().view(-1), att_dst.contiguous().view(-1)
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, adj, w, att_src, att_dst, bias)
+        B, N, Fi = x.shape
+        HC = w.shape[0]
+        H, C = heads, HC // heads
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert w.shape == (H * C, Fi) and att_src.numel() == HC and att_dst.numel() == HC
+        dev = x.device
+        out = torch.empty(B, N, HC if concat else C, device=dev, dtype=_f32)
+        y = torch.empty(B, N, HC, device=dev, dtype=_f32)
+        o = torch.empty(B, N, HC, device=dev, dtype=_f32)
+        stats = torch.empty(4, B, N, H, device=dev, dtype=_f32)       # s_src, s_dst, row max, row sum
+        bits = torch.empty(B, N, (N + 31) // 32, device=dev, dtype=torch.int32)
+        _call("gcm_dense_gatconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w), _hip.ptr(att_src),
+              _hip.ptr(att_dst), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(y), _hip.ptr(o), _hip.ptr(stats[0]),
+              _hip.ptr(stats[1]), _hip.ptr(stats[2]), _hip.ptr(stats[3]), _hip.ptr(bits), B, N, Fi, H, C,
+              int(concat), int(add_loop), float(slope), _hip.stream())
+        ctx.save_for_backward(x, w, att_src, att_dst, y, stats, bits)
+        ctx.cfg = (H, C, int(concat), float(slope), bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w, att_src, att_dst, y, stats, bits = ctx.saved_tensors
+        H, C, concat, slope, has_bias = ctx.cfg
+        B, N, Fi = x.shape
+        need_x, _, need_w, need_as, need_ad, need_b = ctx.needs_input_grad[:6]
+        g_out = g_out.contiguous()
+        lib = _hip.lib()
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(w) if need_w else None
+        g_as = torch.empty(H * C, device=x.device, dtype=_f32) if need_as else None
+        g_ad = torch.empty(H * C, device=x.device, dtype=_f32) if need_ad else None
+        g_b = torch.empty(H * C if concat else C, device=x.device, dtype=_f32) if need_b and has_bias else None
+        ws_bytes = lib.gcm_dense_gatconv_bwd_workspace_bytes(B, N, Fi, H, C, concat)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_gatconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w), _hip.ptr(att_src),
+              _hip.ptr(att_dst), _hip.ptr(y), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(stats[2]),
+              _hip.ptr(stats[3]), _hip.ptr(bits), _hip.ptr(g_x), _hip.ptr(g_w),
+              _hip.ptr(g_as), _hip.ptr(g_ad), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, H, C, concat,
+              slope, _hip.stream())
+        return g_x, None, g_w, g_as, g_ad, g_b, None, None, None, None
+
+
+def dense_gatconv(x, adj, w, att_src, att_dst, bias, heads, concat, add_loop, slope):
+    """-> out; att_src / att_dst are viewed flat [H*C] (their gradients come back in the same shape)."""
+    return _DenseGATConv.apply(x, adj, w, att_src.view(-1), att_dst.view(-1), bias, heads, concat, add_loop,
+                               slope)
+
+
+class _CsrGATConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, att_src, att_dst, bias, graph, heads, concat, add_self_loops, slope):
+        x, w = x.contiguous(), w.contiguous()
+        att_src, att_dst = att_src.contiguous().view(-1), att_dst.contiguous().view(-1)
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, w, att_src, att_dst, bias)
+        M, Fi = x.shape
+        HC = w.shape[0]
+        H, C = heads, HC // heads
+        assert M == graph.M and w.shape == (H * C, Fi)
+        dev = x.device
+        out = torch.empty(M, HC if concat else C, device=dev, dtype=_f32)
+        y = torch.empty(M, HC, device=dev, dtype=_f32)
+        o = torch.empty(M, HC, device=dev, dtype=_f32)
+        stats = torch.empty(4, M, H, device=dev, dtype=_f32)
+        _call("gcm_csr_gatconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(w),
+              _hip.ptr(att_src), _hip.ptr(att_dst), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(y), _hip.ptr(o),
+              _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(stats[2]), _hip.ptr(stats[3]), M, graph.E, Fi,
+              H, C, int(concat), int(add_self_loops), float(slope), _hip.stream())
+        ctx.save_for_backward(x, w, att_src, att_dst, y, stats)
+        ctx.graph = graph
+        ctx.cfg = (H, C, int(concat), int(add_self_loops), float(slope), bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w, att_src, att_dst, y, stats = ctx.saved_tensors
+        H, C, concat, loops, slope, has_bias = ctx.cfg
+        graph = ctx.graph
+        M, Fi = x.shape
+        E = graph.E
+        need_x, need_w, need_as, need_ad, need_b = ctx.needs_input_grad[:5]
+        g_out = g_out.contiguous()
+        lib = _hip.lib()
+        col_ptr = rows = perm = None
+        if E > 0 and (need_x or need_w or need_as or need_ad):
+            col_ptr, rows, perm = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(w) if need_w else None
+        g_as = torch.empty(H * C, device=x.device, dtype=_f32) if need_as else None
+        g_ad = torch.empty(H * C, device=x.device, dtype=_f32) if need_ad else None
+        g_b = torch.empty(H * C if concat else C, device=x.device, dtype=_f32) if need_b and has_bias else None
+        ws_bytes = lib.gcm_csr_gatconv_bwd_workspace_bytes(M, E, Fi, H, C, concat)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_gatconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w), _hip.ptr(att_src),
+              _hip.ptr(att_dst), _hip.ptr(y), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(stats[2]),
+              _hip.ptr(stats[3]), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_as),
+              _hip.ptr(g_ad), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, M, E, Fi, H, C, concat, loops, slope,
+              _hip.stream())
+        return g_x, g_w, g_as, g_ad, g_b, None, None, None, None, None
+
+
+def csr_gatconv(x, w, att_src, att_dst, bias, graph, heads, concat, add_self_loops, slope):
+    return _CsrGATConv.apply(x, w, att_src.view(-1), att_dst.view(-1), bias, graph, heads, concat,
+                             add_self_loops, slope)
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

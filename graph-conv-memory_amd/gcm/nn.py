@@ -183,6 +183,120 @@ class GCNConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
 
 
+def _gat_check(dropout, edge_dim=None):
+    """Widths beyond the kernels' (in_channels or heads * out_channels > 128) raise at the first call."""
+    if dropout < 0 or dropout > 1:
+        raise ValueError(f"dropout must be in [0, 1]; got {dropout}")
+    if edge_dim is not None:
+        raise NotImplementedError("GATConv(edge_dim=...) is not implemented: edge features are not attended to")
+
+
+def _gat_params(conv, in_channels, out_channels, heads, concat, bias, att_shape):
+    conv.in_channels, conv.out_channels, conv.heads, conv.concat = in_channels, out_channels, heads, concat
+    conv.lin = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
+    conv.att_src = torch.nn.Parameter(torch.empty(att_shape))
+    conv.att_dst = torch.nn.Parameter(torch.empty(att_shape))
+    conv.bias = torch.nn.Parameter(torch.empty(heads * out_channels if concat else out_channels)) if bias else None
+
+
+def _gat_reset(conv):
+    torch.nn.init.xavier_uniform_(conv.lin.weight)
+    bound = (6.0 / (conv.heads + conv.out_channels)) ** 0.5      # PyG's glorot on [.., H, C]
+    for att in (conv.att_src, conv.att_dst):
+        torch.nn.init.uniform_(att, -bound, bound)
+    if conv.bias is not None:
+        torch.nn.init.zeros_(conv.bias)
+
+
+def _gat_dropout(conv):
+    if conv.training and conv.dropout > 0:
+        raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
+
+
+class DenseGATConv(torch.nn.Module):
+    """PyG's DenseGATConv (GAT v1): adj[b,i,j] != 0 means i attends to j (only the pattern matters; the
+    diagonal is set when add_loop); y = x W^T viewed [B,N,H,C], e_ij = leaky_relu(<y_i, att_dst> +
+    <y_j, att_src>), alpha = softmax_j over the pattern, out_i = sum_j alpha_ij y_j, heads concatenated
+    (or averaged), + bias, * mask.  A row with no neighbour aggregates nothing (out = bias), where PyG's
+    dense formula gives NaN.  Forward and backward are HIP kernels (csrc/gatconv.hip); adj gets no
+    gradient.  Attention dropout is not implemented (dropout > 0 raises in training mode).  Not a
+    DenseGraphConv: DenseGCM runs a GAT stack through its layered path."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0,
+                 bias=True):
+        super().__init__()
+        _gat_params(self, in_channels, out_channels, heads, concat, bias, (1, 1, heads, out_channels))
+        self.negative_slope, self.dropout = negative_slope, dropout
+        _gat_check(dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _gat_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=True):
+        _gat_dropout(self)
+        x = x.unsqueeze(0) if x.dim() == 2 else x
+        adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
+        if adj.dtype != torch.float32:
+            raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
+        if adj.shape[0] != x.shape[0]:
+            adj = adj.expand(x.shape[0], -1, -1)
+        out = _ops.dense_gatconv(x, adj.detach(), self.lin.weight, self.att_src, self.att_dst, self.bias,
+                                 self.heads, self.concat, add_loop, self.negative_slope)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+
+
+class GATConv(torch.nn.Module):
+    """PyG's GATConv (GAT v1, flow source_to_target): edge_index [2,E] = (source, sink), x [M,F].  With
+    add_self_loops every i -> i edge is removed and one loop per node added; duplicate edges are separate
+    terms of the softmax, which runs per destination over its incoming edges (a node with none: out =
+    bias).  edge_attr is accepted and ignored, as PyG does without edge_dim.  Uses the
+    `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed here.  Forward and
+    backward are HIP kernels (csrc/gatconv.hip).  Not implemented (NotImplementedError): attention
+    dropout in training mode, edge_dim, return_attention_weights.  Not a GraphConv: SparseGCM runs a GAT
+    stack through its generic path."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0,
+                 add_self_loops=True, edge_dim=None, fill_value="mean", bias=True):
+        super().__init__()
+        _gat_params(self, in_channels, out_channels, heads, concat, bias, (1, heads, out_channels))
+        self.negative_slope, self.dropout = negative_slope, dropout
+        self.add_self_loops, self.edge_dim, self.fill_value = add_self_loops, edge_dim, fill_value
+        _gat_check(dropout, edge_dim)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _gat_reset(self)
+
+    def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None):
+        if return_attention_weights is not None:
+            raise NotImplementedError("GATConv(return_attention_weights=...) is not implemented")
+        _gat_dropout(self)
+        _hip.on_device(self.lin.weight)     # a CPU module fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("GATConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        return _ops.csr_gatconv(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
+                                self.concat, self.add_self_loops, self.negative_slope)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+
+
+class GATv2Conv(torch.nn.Module):
+    """Placeholder for PyG's GATv2Conv, so a port fails with a clear message instead of an ImportError."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("GATv2Conv is not implemented; gcm.nn has GATConv / DenseGATConv (GAT v1)")
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).

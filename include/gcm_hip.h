@@ -378,6 +378,50 @@ int gcm_csr_gcnconv_bwd(const float* g_out, const float* x, const float* agg, co
                         size_t workspace_bytes, int64_t M, int64_t E, int Fi, int Fo, int normalize,
                         int add_self_loops, gcm_stream_t stream);
 
+/* ---- GATConv / DenseGATConv (PyG, GAT v1; csrc/gatconv.hip) --------------------- */
+
+/* Dense: y = x W^T [B,N,H*C]; s_src[b,j,h] = <y[b,j,h,:], att_src[h,:]>, s_dst likewise;
+ * e[b,i,j,h] = leaky_relu(s_dst[b,i,h] + s_src[b,j,h], negative_slope) where adj[b,i,j] != 0 (the
+ * diagonal counted as nonzero when add_loop; only the pattern matters), alpha = softmax over j;
+ * o[b,i,h,:] = sum_j alpha y[b,j,h,:] (0 for a row with no neighbour); out = o [B,N,H*C] + bias when
+ * concat, else mean_h o [B,N,C] + bias.  x [B,N,Fi], adj [B,N,N], w [H*C,Fi], att_src/att_dst [H*C],
+ * bias [H*C or C] or NULL.  o [B,N,H*C] is scratch.  Saved for the backward (all required): y; s_src, s_dst,
+ * row_m (max score, -inf for an empty row), row_l (softmax sum) [B,N,H]; bits [B,N,ceil(N/32)]
+ * (the pattern).  Fi, H*C <= 128, any N; GCM_EUNSUPPORTED otherwise. */
+int gcm_dense_gatconv_fwd(const float* x, const float* adj, const float* w, const float* att_src,
+                          const float* att_dst, const float* bias, float* out, float* y, float* o, float* s_src,
+                          float* s_dst, float* row_m, float* row_l, unsigned* bits, int B, int N, int Fi, int H,
+                          int C, int concat, int add_loop, float negative_slope, gcm_stream_t stream);
+
+/* Backward of the above (the adjacency gets no gradient).  Outputs (each may be NULL to skip): g_x
+ * [B,N,Fi], g_w [H*C,Fi], g_att_src / g_att_dst [H*C], g_bias [H*C or C] (all overwritten). */
+size_t gcm_dense_gatconv_bwd_workspace_bytes(int B, int N, int Fi, int H, int C, int concat);
+int gcm_dense_gatconv_bwd(const float* g_out, const float* x, const float* w, const float* att_src,
+                          const float* att_dst, const float* y, const float* s_src, const float* s_dst, const float* row_m, const float* row_l, const unsigned* bits,
+                          float* g_x, float* g_w, float* g_att_src, float* g_att_dst, float* g_bias,
+                          void* workspace, size_t workspace_bytes, int B, int N, int Fi, int H, int C,
+                          int concat, float negative_slope, gcm_stream_t stream);
+
+/* Sparse: the same layer over a destination CSR (row_ptr [M+1], col [E] = sources); the softmax runs
+ * per destination over its CSR entries, duplicates included.  add_self_loops: every i -> i entry is
+ * skipped and node i gets one loop term.  x [M,Fi]; the other operands as the dense layer's with
+ * rows M; row_m / row_l [M,H]. */
+int gcm_csr_gatconv_fwd(const float* x, const int64_t* row_ptr, const int64_t* col, const float* w,
+                        const float* att_src, const float* att_dst, const float* bias, float* out, float* y,
+                        float* o, float* s_src, float* s_dst, float* row_m, float* row_l, int64_t M, int64_t E,
+                        int Fi, int H, int C, int concat, int add_self_loops, float negative_slope,
+                        gcm_stream_t stream);
+
+/* Backward.  col_ptr/rows/perm: the CSC by source as for gcm_csr_graphconv_bwd (may be NULL when
+ * E == 0).  Outputs (NULL to skip) as the dense backward's. */
+size_t gcm_csr_gatconv_bwd_workspace_bytes(int64_t M, int64_t E, int Fi, int H, int C, int concat);
+int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_ptr, const int64_t* col,
+                        const int64_t* col_ptr, const int64_t* rows, const int64_t* perm, const float* w,
+                        const float* att_src, const float* att_dst, const float* y, const float* s_src, const float* s_dst, const float* row_m, const float* row_l,
+                        float* g_x, float* g_w, float* g_att_src, float* g_att_dst, float* g_bias,
+                        void* workspace, size_t workspace_bytes, int64_t M, int64_t E, int Fi, int H, int C,
+                        int concat, int add_self_loops, float negative_slope, gcm_stream_t stream);
+
 /* ---- LearnedEdge (src/gcm/edge_selectors/learned.py:53-125) ------------------- */
 
 /* learned.py:66-72: pairs[b, j, :] = cat(nodes[b, cur_b], nodes[b, j]) for j < cur_b, zero rows
