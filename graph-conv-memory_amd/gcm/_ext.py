@@ -11,7 +11,6 @@ _EXT_DIR = os.path.join(_LIB_DIR, "ext")
 _NAME = "gcm_torch_ext"
 _SO = os.path.join(_EXT_DIR, _NAME + ".so")
 _SRC = os.path.join(os.path.dirname(_HERE), "csrc", "torch_ext", "step_ext.cpp")
-_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
 
 _mod = None
 
@@ -20,7 +19,7 @@ def build(verbose=False):
     """Compile the extension into gcm/_lib/ext/ (host C++ only; links libgcm_hip.so)."""
     import torch
     from torch.utils import cpp_extension
-    from . import _hip
+    from . import _abi, _hip
     _hip.lib()   # libgcm_hip.so must exist (and is then already mapped when the module loads)
     os.makedirs(_EXT_DIR, exist_ok=True)
     global _mod
@@ -28,7 +27,7 @@ def build(verbose=False):
         name=_NAME, sources=[_SRC],
         # host C++ only; the ROCm include path is for c10/hip (current stream / device of the
         # process), whose library torch has loaded already
-        extra_include_paths=[_INCLUDE, os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")],
+        extra_include_paths=[_abi.INCLUDE, os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")],
         extra_cflags=["-O2", "-std=c++17", "-Wno-deprecated-declarations"]
         + (["-DGCM_HOST_PROF"] if os.environ.get("GCM_HOST_PROF") == "1" else []),   # (tools/hosttime.py: segments of RowsFast.step)
         extra_ldflags=[f"-L{_LIB_DIR}", "-lgcm_hip", "-Wl,-rpath,'$$ORIGIN/..'",

@@ -62,7 +62,9 @@ int gcm_version(void);
  * and gcm_edge_distance_step_cached / gcm_learned_step_cached(_functional) / gcm_learned_bptt_cached gained pointer
  * arguments mid-signature; 7: gcm_learned_step_bwd, the single-step LearnedEdge backward, was retired).  A binding
  * compares gcm_abi_version() with the GCM_ABI_VERSION it was written against before any other call (gcm/_hip.py
- * does; INTEGRATION.md shows the stub) - stale ctypes prototypes would otherwise shift pointers silently. */
+ * does; INTEGRATION.md shows the stub) - stale ctypes prototypes would otherwise shift pointers silently.
+ * The Python binding (gcm/_abi.py) is derived from the text of this file: a declaration, constant or struct member
+ * written in a form that reader cannot map to ctypes fails at import, naming it. */
 #define GCM_ABI_VERSION 7
 int gcm_abi_version(void);
 const char* gcm_status_string(int code);

@@ -23,6 +23,103 @@ def test_library_exports_every_declared_symbol():
     assert lib.gcm_status_string(-2).decode().startswith("shape not supported")
 
 
+_SHAPES_HEADER = """
+#ifndef T_H
+#define T_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef void* gcm_stream_t; /* hipStream_t */
+#define GCM_EBAD (-2) /* negative, parenthesised */
+#define GCM_FOUR 4u
+#define GCM_PLAIN 7
+#define GCM_BYTES (160 * 1024)
+typedef struct gcm_pair { int a, b; int32_t h[4]; const float* p; } gcm_pair;
+int gcm_version(void);
+size_t gcm_bytes(int B, int N);
+const char* gcm_name(int code);
+/* spread over several lines, comments between the parameters */
+int gcm_many(const float* const* rows,   /* host array of device pointers */
+             size_t* sizes,              // written
+             long stride_a, long stride_b,
+             int64_t M, float eps, const gcm_pair* pairs,
+             gcm_stream_t stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_shapes():
+    """gcm/_abi.py on every declaration shape include/gcm_hip.h uses."""
+    import ctypes as C
+    from gcm import _abi
+    text = _abi.strip_comments(_SHAPES_HEADER)
+    assert _abi.prototypes(text) == {
+        "gcm_version": (C.c_int, []),
+        "gcm_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+        "gcm_name": (C.c_char_p, [C.c_int]),
+        "gcm_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    }
+    assert _abi.constants(text) == {"GCM_EBAD": -2, "GCM_FOUR": 4, "GCM_PLAIN": 7}     # the product is skipped
+    assert _abi.struct_fields(text, "gcm_pair") == [("a", C.c_int), ("b", C.c_int), ("h", C.c_int32 * 4), ("p", C.c_void_p)]
+    for bad in ("int gcm_odd(int a, unsigned b);", "double gcm_odd(int a);", "int gcm_odd(int a, long long b);"):
+        with pytest.raises(TypeError, match="gcm_odd"):       # never guessed: raises, naming the function
+            _abi.prototypes(text + bad)
+    with pytest.raises(TypeError):
+        _abi.prototypes(text + "int gcm_stray;")
+
+
+def _top_level_commas(params):
+    depth = n = 0
+    for ch in params:
+        depth += ch in "(["
+        depth -= ch in ")]"
+        n += ch == "," and depth == 0
+    return n
+
+
+def test_prototype_argument_counts_match_header():
+    """Every bound prototype has as many argtypes as its declaration has top-level commas, plus one - counted on the
+    header text, independently of the reader's type mapping."""
+    from gcm import _hip
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gcm_hip.h")).read(), flags=re.S)
+    decls = re.findall(r"\b(gcm_[a-z0-9_]+)\s*\((.*?)\)\s*;", header, flags=re.S)
+    assert len(decls) == len(_hip.PROTOTYPES) == 150      # an ABI revision that adds or retires entry points updates this
+    for name, params in decls:
+        want = 0 if params.strip() == "void" else _top_level_commas(params) + 1
+        assert len(_hip.PROTOTYPES[name][1]) == want, name
+
+
+def test_constants_come_from_header():
+    from gcm import _hip
+    header = open(os.path.join(ROOT, "include", "gcm_hip.h")).read()
+    assert f"#define GCM_ABI_VERSION {_hip.ABI_VERSION}\n" in header
+    assert _hip.GCM_EUNSUPPORTED == -2 and _hip.FLAG_WINDOW == 128 and _hip.STEP_FOUR_WAVES == 256
+    assert _hip.BPTT_MLP_BLOCKS == 256 and _hip.SPATIAL_MAX_COLS == 32
+    assert _hip.DIR == {"forward": 1, "backward": 2, "both": 3}
+    assert not hasattr(_hip, "SPATIAL_MAX_LDS")             # an expression, not a literal: left to C
+
+
+def test_selector_desc_layout():
+    """SelectorDesc against struct gcm_selector_desc: member names and order from the header text, and the size the C
+    compiler gives it on LP64 with natural alignment:
+      kind, n_hops 2 x 4 = 8 | hops[16] 64 -> 72 | direction, mode, max_distance 3 x 4 -> 84 | 4 padding -> 88 |
+      dist_param 8 -> 96 | a0, a1, b0, b1, bidirectional 5 x 4 -> 116 | 4 padding -> 120 | cur_rows 8 -> 128 |
+      n_cur_rows 4 -> 132 | 4 tail padding (alignment 8) -> 136."""
+    import ctypes as C
+    from gcm import _hip
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "gcm_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct gcm_selector_desc \{(.*?)\} gcm_selector_desc;", header, flags=re.S).group(1)
+    names = [n for member in body.split(";") if member.strip()
+             for n in re.findall(r"(\w+)(?:\[\d+\])?\s*(?:,|$)", member.strip())]
+    assert [f[0] for f in _hip.SelectorDesc._fields_] == names and len(names) == 14
+    assert C.sizeof(_hip.SelectorDesc) == 136
+    assert (_hip.SelectorDesc.hops.offset, _hip.SelectorDesc.hops.size) == (8, 64)
+    assert (_hip.SelectorDesc.dist_param.offset, _hip.SelectorDesc.cur_rows.offset, _hip.SelectorDesc.n_cur_rows.offset) == (88, 120, 128)
+
+
 def test_argument_errors_without_gpu():
     """Host-side validation returns GCM_EINVAL before anything touches a device."""
     from gcm import _hip

@@ -878,7 +878,7 @@ def test_rows_colcache_c_abi_four_and_eight_waves(kind):
     st, p = _hip.stream(), _hip.ptr
     lay = (ctypes.c_size_t * 6)()
     assert lib.gcm_dense_rows_layout(B, N, F, H, H, ctypes.addressof(lay)) == 0
-    FOUR = 256   # GCM_STEP_FOUR_WAVES
+    FOUR = _hip.STEP_FOUR_WAVES
 
     def chain(form):
         nodes, adj = torch.zeros(B, N, F, device=DEV), torch.zeros(B, N, N, device=DEV)

@@ -13,10 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def child(path):
     import torch
-    lib = ctypes.CDLL(path)
-    P, I, F_, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    lib.gcm_edge_distance_pre.argtypes = [P, P, P, P, I, F_, P, I, I, I, I, P, Z, I, I, I, P]
-    lib.gcm_edge_distance_pre.restype = I
+    sys.path.insert(0, os.path.join(ROOT, "graph-conv-memory_amd"))
+    from gcm import _hip
+    lib = _hip.bind(ctypes.CDLL(path), names=["gcm_edge_distance_pre"])   # (a partial build: bind what is called)
     B, N, F = 256, 128, 64
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(3)

@@ -3,20 +3,17 @@ NOT part of the product: nothing under graph-conv-memory_amd/gcm loads this libr
 (libgcm_hip.so) exports none of these entry points."""
 import ctypes
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(_HERE), "graph-conv-memory_amd"))
+from gcm import _abi, _hip  # noqa: E402
+
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "graph-conv-memory_amd", "gcm", "_lib", "libgcm_hip_debug.so")
-_P, _I = ctypes.c_void_p, ctypes.c_int
-PROTOTYPES = {
-    "gcm_debug_time_next_launch": (_I, [_P, _P]),
-    "gcm_debug_time_rows_rollout": (_I, [_P] * 5 + [_I, _P, _I, _I, _I] + [_P] * 4 + [_I] * 6 + [_P]),
-    "gcm_debug_time_cached_rollout": (_I, [_P] * 5 + [_I, _P, _P, _I, _I, _I] + [_P] * 7 + [_I] * 6 + [_P]),
-    "gcm_debug_empty_graph_cadence": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
-    "gcm_debug_empty_launch_duration": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_float),
-                                              ctypes.POINTER(ctypes.c_float)]),
-    # product entry points the aids are used with (the same kernels, built from the same sources)
-    "gcm_dense_rows_cached_weight_image": (_I, [_P, _P, _I, _I, _I, _P]),
-}
+# the aids of include/gcm_hip_debug.h + the product entry point they are used with (the same kernels, built from
+# the same sources); float* results are c_void_p: pass ctypes.byref(c_float())
+PROTOTYPES = dict(_abi.prototypes(_abi.header("gcm_hip_debug.h")),
+                  gcm_dense_rows_cached_weight_image=_hip.PROTOTYPES["gcm_dense_rows_cached_weight_image"])
 _lib = None
 
 
@@ -25,11 +22,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not found: `make -C graph-conv-memory_amd/csrc debug`")
-        h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = h
+        _lib = _hip.bind(ctypes.CDLL(LIB_PATH), PROTOTYPES)
     return _lib
 
 

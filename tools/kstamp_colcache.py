@@ -33,7 +33,7 @@ saved = torch.empty(lay[0], device=dev)
 flags = torch.zeros(1, dtype=torch.int32, device=dev)
 
 
-FOUR = 256   # GCM_STEP_FOUR_WAVES: the four-wave kernel (the one the stamps are in) where the eight-wave form exists
+FOUR = _hip.STEP_FOUR_WAVES   # the four-wave kernel (the one the stamps are in) where the eight-wave form exists
 
 
 def run(lib, cur, record, four=False):

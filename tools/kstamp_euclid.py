@@ -3,10 +3,14 @@
 in-kernel stamps (diagnostic build: make -C graph-conv-memory_amd/csrc stamps6).  Dev tool."""
 import ctypes
 import os
+import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "graph-conv-memory_amd"))
+from gcm import _hip  # noqa: E402
+
 lib = ctypes.CDLL(os.environ.get("STAMPLIB") or os.path.join(ROOT, "graph-conv-memory_amd", "gcm", "_lib", "libgcm_hip_stamps6.so"))
 B, N, F = 256, 128, 64
 CUR = int(os.environ.get("CUR", 100))
@@ -20,8 +24,7 @@ ws = torch.empty(B * F + B, device=dev)
 V = ctypes.c_void_p
 p = lambda t: V(t.data_ptr())
 st = V(torch.cuda.current_stream().cuda_stream)
-lib.gcm_edge_distance_pre.argtypes = [V, V, V, V, ctypes.c_int, ctypes.c_float, V] + [ctypes.c_int] * 4 + \
-    [V, ctypes.c_size_t] + [ctypes.c_int] * 3 + [V]
+_hip.bind(lib, names=["gcm_edge_distance_pre"])
 names = ["node rows + chunk 0 -> LDS (+barrier)", "|n|^2, |c|^2 (+barrier)", "chunk 0: next chunk's loads issued, MFMA + sqrt",
          "chunk 1 -> LDS (+barrier)", "|c|^2, chunk 1: MFMA + sqrt", "reductions, column tiles, emit"]
 acc, R = [0.0] * 6, 20

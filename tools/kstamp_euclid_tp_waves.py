@@ -1,13 +1,13 @@
 import ctypes, os, sys
-ROOT="/root/repo"
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0]=[ROOT, os.path.join(ROOT,"graph-conv-memory_amd")]
 import torch, bench
+from gcm import _hip
 c=bench.CONFIGS["cfg3"]; dev=torch.device("cuda",0)
-lib=ctypes.CDLL(os.environ["STAMPLIB"])
+lib=_hip.bind(ctypes.CDLL(os.environ["STAMPLIB"]),names=["gcm_euclid_rollout_tp_decide"])
 B,N,F=c["B"],c["N"],c["F"]; T=128
 obs=torch.rand(T,B,F,device=dev)
 bits=torch.empty(T,B,4,dtype=torch.int32,device=dev)
-lib.gcm_euclid_rollout_tp_decide.argtypes=[ctypes.c_void_p,ctypes.c_float,ctypes.c_void_p,ctypes.c_void_p]+[ctypes.c_int]*4+[ctypes.c_void_p]
 for _ in range(3):
     rc=lib.gcm_euclid_rollout_tp_decide(obs.data_ptr(),2.0,None,bits.data_ptr(),T,B,N,F,None)
     torch.cuda.synchronize()
