@@ -19,6 +19,10 @@ _lib = None
 _HEADER = _abi.header("gcm_hip.h")
 PROTOTYPES = _abi.prototypes(_HEADER)
 _CONSTANTS = _abi.constants(_HEADER)
+# the section gcm_hip.h includes from gcm_hip_aggr.h (mean / max aggregation), read the same way
+_AGGR_HEADER = _abi.header("gcm_hip_aggr.h")
+AGGR_PROTOTYPES = _abi.prototypes(_AGGR_HEADER)
+_CONSTANTS.update(_abi.constants(_AGGR_HEADER))
 globals().update({name[4:]: value for name, value in _CONSTANTS.items()})   # GCM_ACT_TANH -> ACT_TANH, ...
 GCM_EUNSUPPORTED = _CONSTANTS["GCM_EUNSUPPORTED"]
 DIR = {d: _CONSTANTS["GCM_DIR_" + d.upper()] for d in ("forward", "backward", "both")}
@@ -54,6 +58,7 @@ def lib():
         # (GCM_HIP_LIB: a diagnostic build of the same library - csrc/Makefile `stamps*`, `exp` - for the
         #  dev tools under tools/; never set by the product)
         handle = bind(ctypes.CDLL(os.environ.get("GCM_HIP_LIB") or _LIB_PATH))
+        bind(handle, AGGR_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

@@ -800,6 +800,132 @@ def csr_gatconv(x, w, att_src, att_dst, bias, graph, heads, concat, add_self_loo
                              add_self_loops, slope)
 
 
+# ---------------------------------------------------------------------------
+# mean / max aggregation: GraphConv(aggr=...), SAGEConv and their dense forms (csrc/aggrconv.hip)
+# ---------------------------------------------------------------------------
+AGGR = {"mean": _hip.AGGR_MEAN, "max": _hip.AGGR_MAX}
+
+
+class _DenseAggrConv(torch.autograd.Function):
+    """out = agg(adj, x) W_rel^T + x W_root^T + bias; w_root and bias may be None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, w_rel, w_root, bias, aggr):
+        x, adj, w_rel = x.contiguous(), adj.contiguous(), w_rel.contiguous()
+        w_root = None if w_root is None else w_root.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, adj, w_rel, w_root, bias)
+        B, N, Fi = x.shape
+        Fo = w_rel.shape[0]
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert w_rel.shape == (Fo, Fi) and (w_root is None or w_root.shape == (Fo, Fi))
+        dev = x.device
+        out = torch.empty(B, N, Fo, device=dev, dtype=_f32)
+        agg = torch.empty(B, N, Fi, device=dev, dtype=_f32)
+        deg = dinv = winner = None
+        if aggr == _hip.AGGR_MEAN:
+            deg = torch.empty(B, N, device=dev, dtype=_f32)
+            dinv = torch.empty(B, N, device=dev, dtype=_f32)
+        else:
+            winner = torch.empty(B, N, Fi, device=dev, dtype=torch.int16)
+        _call("gcm_dense_aggrconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_rel), _hip.ptr(w_root), _hip.ptr(bias),
+              _hip.ptr(out), _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), _hip.ptr(winner), B, N, Fi, Fo, aggr,
+              _hip.stream())
+        ctx.save_for_backward(x, adj, w_rel, w_root, agg, deg, dinv, winner)
+        ctx.aggr, ctx.has_bias = aggr, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, w_rel, w_root, agg, deg, dinv, winner = ctx.saved_tensors
+        B, N, Fi = x.shape
+        Fo = w_rel.shape[0]
+        need_x, need_adj, need_wrel, need_wroot, need_b, _ = ctx.needs_input_grad
+        need_b = need_b and ctx.has_bias
+        need_wroot = need_wroot and w_root is not None
+        need_adj = need_adj and ctx.aggr == _hip.AGGR_MEAN
+        g_out = g_out.contiguous()
+        dev = x.device
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_wrel = torch.empty_like(w_rel) if need_wrel else None
+        g_wroot = torch.empty_like(w_root) if need_wroot else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws_bytes = _hip.lib().gcm_dense_aggrconv_bwd_workspace_bytes(B, N, Fi, Fo)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_dense_aggrconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_rel), _hip.ptr(w_root),
+              _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), _hip.ptr(winner), _hip.ptr(g_x), _hip.ptr(g_adj),
+              _hip.ptr(g_wrel), _hip.ptr(g_wroot), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, ctx.aggr,
+              _hip.stream())
+        return g_x, g_adj, g_wrel, g_wroot, g_b, None
+
+
+def dense_aggrconv(x, adj, w_rel, w_root, bias, aggr):
+    """aggr: "mean" (adj values are weights and get a gradient) or "max" (pattern only: pass adj detached)."""
+    return _DenseAggrConv.apply(x, adj, w_rel, w_root, bias, AGGR[aggr])
+
+
+class _CsrAggrConv(torch.autograd.Function):
+    """x [M,Fi]; w_edge [E] in CSR order or None (unit weights)."""
+
+    @staticmethod
+    def forward(ctx, x, w_edge, w_rel, w_root, bias, graph, aggr):
+        x, w_rel = x.contiguous(), w_rel.contiguous()
+        w_root = None if w_root is None else w_root.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        w_edge = None if w_edge is None else w_edge.contiguous()
+        _hip.on_device(x, w_edge, w_rel, w_root, bias)
+        M, Fi = x.shape
+        Fo = w_rel.shape[0]
+        E = graph.E
+        assert M == graph.M
+        assert w_rel.shape == (Fo, Fi) and (w_root is None or w_root.shape == (Fo, Fi))
+        dev = x.device
+        out = torch.empty(M, Fo, device=dev, dtype=_f32)
+        agg = torch.empty(M, Fi, device=dev, dtype=_f32)
+        winner = torch.empty(M, Fi, device=dev, dtype=torch.int32) if aggr == _hip.AGGR_MAX else None
+        _call("gcm_csr_aggrconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(w_edge),
+              _hip.ptr(w_rel), _hip.ptr(w_root), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(agg), _hip.ptr(winner), M, E,
+              Fi, Fo, aggr, _hip.stream())
+        ctx.save_for_backward(x, w_edge, w_rel, w_root, agg, winner)
+        ctx.graph, ctx.aggr, ctx.has_bias = graph, aggr, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_edge, w_rel, w_root, agg, winner = ctx.saved_tensors
+        graph = ctx.graph
+        M, Fi = x.shape
+        Fo = w_rel.shape[0]
+        E = graph.E
+        need_x, need_we, need_wrel, need_wroot, need_b, _, _ = ctx.needs_input_grad
+        need_b = need_b and ctx.has_bias
+        need_wroot = need_wroot and w_root is not None
+        need_we = need_we and w_edge is not None
+        g_out = g_out.contiguous()
+        dev = x.device
+        col_ptr = rows = perm = dst = None
+        if (need_x or need_we) and E > 0:
+            col_ptr, rows, perm = graph.csc()
+            dst = graph.dst_csr()
+        g_x = torch.empty_like(x) if need_x else None
+        g_we = torch.zeros_like(w_edge) if need_we else None
+        g_wrel = torch.empty_like(w_rel) if need_wrel else None
+        g_wroot = torch.empty_like(w_root) if need_wroot else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws_bytes = _hip.lib().gcm_csr_aggrconv_bwd_workspace_bytes(M, E, Fi, Fo)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_csr_aggrconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(agg), _hip.ptr(graph.row_ptr),
+              _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_edge),
+              _hip.ptr(winner), _hip.ptr(w_rel), _hip.ptr(w_root), _hip.ptr(g_x), _hip.ptr(g_we), _hip.ptr(g_wrel),
+              _hip.ptr(g_wroot), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, M, E, Fi, Fo, ctx.aggr, _hip.stream())
+        return g_x, g_we, g_wrel, g_wroot, g_b, None, None
+
+
+def csr_aggrconv(x, w_edge, w_rel, w_root, bias, graph, aggr):
+    return _CsrAggrConv.apply(x, w_edge, w_rel, w_root, bias, graph, AGGR[aggr])
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

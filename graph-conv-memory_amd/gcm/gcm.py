@@ -397,7 +397,7 @@ class DenseGCM(torch.nn.Module):
             convs, acts = [], []
             for mod, ins, outs in g.stages():
                 if isinstance(mod, G.DenseGraphConv):
-                    if ins != [xn, an] or outs != [xn] or len(convs) == 2:
+                    if mod.aggr != "add" or ins != [xn, an] or outs != [xn] or len(convs) == 2:
                         return None
                     convs.append(mod)
                     acts.append(_hip.ACT_NONE)

@@ -28,14 +28,58 @@ class SkinnyLinear(torch.nn.Linear):
         return super().forward(x)
 
 
+_AGGRS = ("add", "mean", "max")
+
+
+def _dense_inputs(x, adj):
+    x = x.unsqueeze(0) if x.dim() == 2 else x
+    adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
+    if adj.dtype != torch.float32:
+        raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
+    if adj.shape[0] != x.shape[0]:
+        adj = adj.expand(x.shape[0], -1, -1)
+    return x, adj
+
+
+def _dense_aggr(x, adj, mask, w_rel, w_root, bias, aggr):
+    """The mean / max form of DenseGraphConv and DenseSAGEConv (csrc/aggrconv.hip).  Max reads only the
+    pattern of adj, which then gets no gradient."""
+    x, adj = _dense_inputs(x, adj)
+    _hip.on_device(w_rel)
+    out = _ops.dense_aggrconv(x, adj.detach() if aggr == "max" else adj, w_rel, w_root, bias, aggr)
+    if mask is not None:
+        out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+    return out
+
+
+def _sparse_aggr(x, edge_index, edge_weight, w_rel, w_root, bias, aggr, name):
+    """The mean / max form of GraphConv and SAGEConv (csrc/aggrconv.hip)."""
+    _hip.on_device(x, w_rel)        # a CPU call fails here, before the index is built
+    graph = getattr(edge_index, "gcm_graph", None)
+    if graph is None or graph.M != x.shape[0]:
+        graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+    if graph.mask is not None:
+        raise ValueError(f"{name} does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+    w = edge_weight
+    if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
+        w = None        # as GraphConv's sum: a wrong-length vector is ignored, unit weights are not loaded
+    if w is not None and graph.csr_perm is not None:
+        w = w[graph.csr_perm]
+    return _ops.csr_aggrconv(x, w, w_rel, w_root, bias, graph, aggr)
+
+
 class DenseGraphConv(torch.nn.Module):
-    """out = lin_rel(adj @ x) + lin_root(x), adj [B,N,N] float, x [B,N,F].
-    Runs as one fused fp32-MFMA kernel (csrc/graphconv.hip)."""
+    """out = lin_rel(agg) + lin_root(x), adj [B,N,N] float (adj[b,i,j]: i aggregates from j), x [B,N,F].
+    aggr="add": agg = adj @ x, one fused fp32-MFMA kernel (csrc/graphconv.hip).
+    aggr="mean": agg_i = (adj @ x)_i / clamp(rowsum(adj)_i, min=1); adj values are weights and get a gradient.
+    aggr="max": agg_ic = max of x_jc over {j: adj_ij != 0}, 0 for an empty row; only the pattern of adj is
+    read and adj gets no gradient.  Mean and max run in csrc/aggrconv.hip; the fused DenseGCM / Sequential
+    paths apply to aggr="add" only."""
 
     def __init__(self, in_channels, out_channels, aggr="add", bias=True):
         super().__init__()
-        if aggr != "add":
-            raise NotImplementedError("only aggr='add' (the reference's usage) is implemented")
+        if aggr not in _AGGRS:
+            raise NotImplementedError(f"aggr='{aggr}' is not implemented: one of {_AGGRS}")
         self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
         self.lin_rel = torch.nn.Linear(in_channels, out_channels, bias=bias)
         self.lin_root = torch.nn.Linear(in_channels, out_channels, bias=False)
@@ -45,6 +89,10 @@ class DenseGraphConv(torch.nn.Module):
         self.lin_root.reset_parameters()
 
     def forward(self, x, adj, mask=None, _act=_hip.ACT_NONE):
+        if self.aggr != "add":
+            if _act != _hip.ACT_NONE:
+                raise ValueError("activation fusion is available for aggr='add' only")
+            return _dense_aggr(x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_rel.bias, self.aggr)
         squeeze = x.dim() == 2
         x = x.unsqueeze(0) if x.dim() == 2 else x
         adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
@@ -69,12 +117,16 @@ class GraphConv(torch.nn.Module):
     sink), x [M,F].  The neighbour reduction is a CSR gather fused with the two linears on
     the matrix cores (csrc/graphconv.hip, k_csr_graphconv_fwd).  When SparseGCM built the
     edge list it attaches a ready CSR (`edge_index.gcm_graph`); any other edge_index is
-    indexed here on the device."""
+    indexed here on the device.
+    aggr="mean": the weighted sum divided by the number of edges into i (not by the weight sum).
+    aggr="max": per channel the largest w_ji * x_j; the gradient goes to the winning edge, the first in CSR
+    order on a tie; duplicate edges compete separately.  A node without an in-edge aggregates 0.  Mean and max
+    run in csrc/aggrconv.hip; SparseGCM's one-call and masked k-hop paths apply to aggr="add" only."""
 
     def __init__(self, in_channels, out_channels, aggr="add", bias=True):
         super().__init__()
-        if aggr != "add":
-            raise NotImplementedError("only aggr='add' (the reference's usage) is implemented")
+        if aggr not in _AGGRS:
+            raise NotImplementedError(f"aggr='{aggr}' is not implemented: one of {_AGGRS}")
         self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
         self.lin_rel = torch.nn.Linear(in_channels, out_channels, bias=bias)
         self.lin_root = torch.nn.Linear(in_channels, out_channels, bias=False)
@@ -84,6 +136,11 @@ class GraphConv(torch.nn.Module):
         self.lin_root.reset_parameters()
 
     def forward(self, x, edge_index, edge_weight=None, _act=_hip.ACT_NONE):
+        if self.aggr != "add":
+            if _act != _hip.ACT_NONE:
+                raise ValueError("activation fusion is available for aggr='add' only")
+            return _sparse_aggr(x, edge_index, edge_weight, self.lin_rel.weight, self.lin_root.weight,
+                                self.lin_rel.bias, self.aggr, "GraphConv(aggr='%s')" % self.aggr)
         graph = getattr(edge_index, "gcm_graph", None)
         if graph is None or graph.M != x.shape[0]:
             graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
@@ -97,6 +154,67 @@ class GraphConv(torch.nn.Module):
             w = w[graph.csr_perm]
         return _ops.csr_graphconv(x, w, self.lin_rel.weight, self.lin_rel.bias,
                                   self.lin_root.weight, graph, _act)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
+class SAGEConv(torch.nn.Module):
+    """PyG's SAGEConv (flow source_to_target): out_i = lin_l(aggr_{j -> i} x_j) + lin_r(x_i), edge_index [2,E] =
+    (source, sink), x [M,F]; aggr "mean" or "max"; no edge weights.  Parameters as PyG 2.x: `lin_l.{weight,bias}`
+    on the aggregate, `lin_r.weight` (absent with root_weight=False).  The same kernels as
+    GraphConv(aggr=...) (csrc/aggrconv.hip).  Not implemented (NotImplementedError): normalize, project, other
+    aggregations.  Not a GraphConv: SparseGCM runs a SAGE stack through its generic path."""
+
+    def __init__(self, in_channels, out_channels, aggr="mean", normalize=False, root_weight=True, project=False,
+                 bias=True):
+        super().__init__()
+        if aggr not in ("mean", "max"):
+            raise NotImplementedError(f"SAGEConv(aggr='{aggr}') is not implemented: 'mean' or 'max'")
+        if normalize:
+            raise NotImplementedError("SAGEConv(normalize=True) is not implemented")
+        if project:
+            raise NotImplementedError("SAGEConv(project=True) is not implemented")
+        self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
+        self.normalize, self.root_weight, self.project = normalize, root_weight, project
+        self.lin_l = torch.nn.Linear(in_channels, out_channels, bias=bias)
+        if root_weight:
+            self.lin_r = torch.nn.Linear(in_channels, out_channels, bias=False)
+
+    def reset_parameters(self):
+        self.lin_l.reset_parameters()
+        if self.root_weight:
+            self.lin_r.reset_parameters()
+
+    def forward(self, x, edge_index):
+        return _sparse_aggr(x, edge_index, None, self.lin_l.weight, self.lin_r.weight if self.root_weight else None,
+                            self.lin_l.bias, self.aggr, "SAGEConv")
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, aggr={self.aggr})"
+
+
+class DenseSAGEConv(torch.nn.Module):
+    """PyG's DenseSAGEConv (mean only): out = lin_rel(adj @ x / clamp(rowsum(adj), min=1)) + lin_root(x), * mask;
+    adj [B,N,N] float (adj[b,i,j]: i aggregates from j; values are weights and get a gradient), x [B,N,F].
+    Parameters as PyG 2.x: `lin_rel.weight` (no bias), `lin_root.{weight,bias}`.  The same kernels as
+    DenseGraphConv(aggr="mean") (csrc/aggrconv.hip).  normalize=True raises NotImplementedError.  Not a
+    DenseGraphConv: DenseGCM runs a SAGE stack through its layered path."""
+
+    def __init__(self, in_channels, out_channels, normalize=False, bias=True):
+        super().__init__()
+        if normalize:
+            raise NotImplementedError("DenseSAGEConv(normalize=True) is not implemented")
+        self.in_channels, self.out_channels, self.normalize = in_channels, out_channels, normalize
+        self.lin_rel = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.lin_root = torch.nn.Linear(in_channels, out_channels, bias=bias)
+
+    def reset_parameters(self):
+        self.lin_rel.reset_parameters()
+        self.lin_root.reset_parameters()
+
+    def forward(self, x, adj, mask=None):
+        return _dense_aggr(x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_root.bias, "mean")
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
@@ -301,7 +419,7 @@ class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
     Sub-modules are registered as module_0, module_1, ... (PyG's naming), so
-    state_dicts are key compatible.  A DenseGraphConv immediately followed by a
+    state_dicts are key compatible.  A DenseGraphConv / GraphConv with aggr="add" immediately followed by a
     bare Tanh/ReLU is executed as ONE kernel (activation in the MFMA epilogue)."""
 
     def __init__(self, input_args, modules):
@@ -332,7 +450,7 @@ class Sequential(torch.nn.Module):
             name, ins, outs = plan[i]
             mod = getattr(self, name)
             fused = None
-            if isinstance(mod, (DenseGraphConv, GraphConv)) and i + 1 < len(plan):
+            if isinstance(mod, (DenseGraphConv, GraphConv)) and mod.aggr == "add" and i + 1 < len(plan):
                 nxt_name, nxt_in, nxt_out = plan[i + 1]
                 nxt = getattr(self, nxt_name)
                 if type(nxt) in _FUSABLE and nxt_in == outs and nxt_out == outs:

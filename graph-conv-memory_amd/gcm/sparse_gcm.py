@@ -111,7 +111,7 @@ class SparseGCM(torch.nn.Module):
             return False
         has = False
         for mod, ins, _ in self.gnn.stages():
-            if isinstance(mod, _nn.GraphConv):
+            if isinstance(mod, _nn.GraphConv) and mod.aggr == "add":     # (mean / max take no row mask)
                 has = True
             elif len(ins) != 1:
                 return False
@@ -134,7 +134,8 @@ class SparseGCM(torch.nn.Module):
                 convs, acts = [], []
                 ok = True
                 for mod, ins, outs in g.stages():
-                    if isinstance(mod, _nn.GraphConv) and ins == g.arg_names and outs == [xn]:
+                    if (isinstance(mod, _nn.GraphConv) and mod.aggr == "add" and ins == g.arg_names
+                            and outs == [xn]):
                         convs.append(mod)
                         acts.append(_hip.ACT_NONE)
                     elif (type(mod) in _nn._FUSABLE and convs and ins == [xn] and outs == [xn]
