@@ -990,6 +990,38 @@ def learned_select_(adj, logits, noise, cur, cutoff):
     return _LearnedSelect.apply(adj, logits, noise, cur, cutoff)
 
 
+class _LearnedSparsemax(torch.autograd.Function):
+    """_LearnedSelect for LearnedEdge(deterministic=True) (learned.py:85-86): row cur of `adj` rewritten in place
+    with the hard sparsemax of the logits (util.Spardmax) - no noise, no cutoff, no sample count."""
+
+    @staticmethod
+    def forward(ctx, adj, logits, cur):
+        logits = logits.contiguous()
+        _hip.on_device(adj, logits, cur)
+        B, N, _ = adj.shape
+        soft = torch.empty(B, N, device=adj.device, dtype=_f32)
+        _call("gcm_learned_sparsemax_fwd", _hip.ptr(logits), _hip.ptr(cur), _hip.ptr(adj), _hip.ptr(soft), B, N,
+              _hip.stream())
+        ctx.mark_dirty(adj)
+        ctx.save_for_backward(soft, cur)
+        return adj
+
+    @staticmethod
+    def backward(ctx, g_adj):
+        soft, cur = ctx.saved_tensors
+        B, N = soft.shape
+        g_adj = g_adj.contiguous()
+        g_logits = torch.empty(B, N, device=g_adj.device, dtype=_f32)
+        _call("gcm_learned_sparsemax_bwd", _hip.ptr(g_adj), _hip.ptr(soft), _hip.ptr(cur), _hip.ptr(g_logits),
+              B, N, _hip.stream())
+        # as _LearnedSelect: both straight-through estimators are identities
+        return g_adj, g_logits, None
+
+
+def learned_sparsemax_select_(adj, logits, cur):
+    return _LearnedSparsemax.apply(adj, logits, cur)
+
+
 # ===========================================================================
 # fused canonical step / time-batched rollout (csrc/fused.hip, csrc/rollout.hip)
 # ===========================================================================
@@ -1512,10 +1544,12 @@ class _LearnedEdgeDefault(torch.autograd.Function):
     """Dense LearnedEdge with the default edge network as ONE autograd node (learned.py:53-113):
     candidate pairs, edge network, gumbel noise, gumbel-softmax + STE + adjacency-row write (in
     place on `adj`, which the caller owns).  `noise` None = draw it here with the device RNG the
-    way torch.nn.functional.gumbel_softmax does."""
+    way torch.nn.functional.gumbel_softmax does.  `deterministic`: the hard sparsemax of the logits
+    instead (learned.py:85-86) - `noise` and `cutoff` are not read, nothing is drawn or allocated for them."""
 
     @staticmethod
-    def forward(ctx, nodes, adj, cur, noise, cutoff, w0, b0, g0, be0, w1, b1, g1, be1, w2, b2, eps0, eps1):
+    def forward(ctx, nodes, adj, cur, noise, cutoff, deterministic, w0, b0, g0, be0, w1, b1, g1, be1, w2, b2,
+                eps0, eps1):
         nodes = nodes.contiguous()
         _hip.on_device(nodes, adj, cur)
         B, N, F = nodes.shape
@@ -1524,13 +1558,18 @@ class _LearnedEdgeDefault(torch.autograd.Function):
         _call("gcm_learned_pairs_fwd", _hip.ptr(nodes), _hip.ptr(cur), _hip.ptr(pairs), B, N, F, st)
         logits, saved = _mlp_fwd(pairs, w0, b0, g0, be0, w1, b1, g1, be1, w2, b2, eps0, eps1)
         logits = logits.view(B, N)
-        if noise is None:
-            noise = -torch.empty_like(logits).exponential_().log()
-        noise = noise.contiguous()
         soft = torch.empty(B, N, device=adj.device, dtype=_f32)
-        _call("gcm_learned_select_fwd", _hip.ptr(logits), _hip.ptr(noise), _hip.ptr(cur), float(cutoff),
-              _hip.ptr(adj), _hip.ptr(soft), B, N, st)
+        if deterministic:
+            _call("gcm_learned_sparsemax_fwd", _hip.ptr(logits), _hip.ptr(cur), _hip.ptr(adj), _hip.ptr(soft),
+                  B, N, st)
+        else:
+            if noise is None:
+                noise = -torch.empty_like(logits).exponential_().log()
+            noise = noise.contiguous()
+            _call("gcm_learned_select_fwd", _hip.ptr(logits), _hip.ptr(noise), _hip.ptr(cur), float(cutoff),
+                  _hip.ptr(adj), _hip.ptr(soft), B, N, st)
         ctx.mark_dirty(adj)
+        ctx.deterministic = bool(deterministic)
         ctx.save_for_backward(soft, cur, *saved)
         ctx.eps = (eps0, eps1)
         ctx.has_bias = (b0 is not None, b1 is not None, b2 is not None)
@@ -1544,8 +1583,8 @@ class _LearnedEdgeDefault(torch.autograd.Function):
         st = _hip.stream()
         g_adj = g_adj.contiguous()
         g_logits = torch.empty(B * N, 1, device=g_adj.device, dtype=_f32)
-        _call("gcm_learned_select_bwd", _hip.ptr(g_adj), _hip.ptr(soft), _hip.ptr(cur), _hip.ptr(g_logits),
-              B, N, st)
+        _call("gcm_learned_sparsemax_bwd" if ctx.deterministic else "gcm_learned_select_bwd", _hip.ptr(g_adj),
+              _hip.ptr(soft), _hip.ptr(cur), _hip.ptr(g_logits), B, N, st)
         g_pairs, pg = _mlp_bwd(g_logits, saved, ctx.eps, ctx.has_bias, ctx.needs_input_grad[0])
         g_nodes = None
         if g_pairs is not None:
@@ -1553,10 +1592,10 @@ class _LearnedEdgeDefault(torch.autograd.Function):
             _call("gcm_learned_pairs_bwd", _hip.ptr(g_pairs), _hip.ptr(cur), _hip.ptr(g_nodes), B, N, F, st)
         # both straight-through estimators are identities: the incoming adjacency receives g_adj
         # unchanged, also at the rewritten entries (learned.py:108-110 adds adj inside the STE)
-        return (g_nodes, g_adj, None, None, None, *pg, None, None)
+        return (g_nodes, g_adj, None, None, None, None, *pg, None, None)
 
 
-def learned_edge_default(net, nodes, adj, cur, noise, cutoff):
+def learned_edge_default(net, nodes, adj, cur, noise, cutoff, deterministic=False):
     """The fused dense LearnedEdge when `net` is the default edge network on device tensors, else None."""
     mods = default_edge_network(net)
     if mods is None or not nodes.is_cuda or nodes.dtype != _f32:
@@ -1564,8 +1603,9 @@ def learned_edge_default(net, nodes, adj, cur, noise, cutoff):
     l0, _, n0, l1, _, n1, l2 = mods
     if l2.out_features != 1 or l0.in_features != 2 * nodes.shape[2]:
         return None
-    return _LearnedEdgeDefault.apply(nodes, adj, cur, noise, cutoff, l0.weight, l0.bias, n0.weight, n0.bias,
-                                     l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n0.eps, n1.eps)
+    return _LearnedEdgeDefault.apply(nodes, adj, cur, noise, cutoff, deterministic, l0.weight, l0.bias, n0.weight,
+                                     n0.bias, l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n0.eps,
+                                     n1.eps)
 
 
 def edge_network_forward(net, x):

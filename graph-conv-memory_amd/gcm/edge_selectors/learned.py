@@ -14,7 +14,11 @@ class LearnedEdge(torch.nn.Module):
     network runs on it as ordinary GEMMs, and gumbel-softmax + threshold + adjacency-row
     write are one fused kernel per direction.  `noise_fn(logits) -> gumbel noise [B, N]`
     may be set to inject the random draws (parity tests); the default draws them with the
-    device RNG the way torch.nn.functional.gumbel_softmax does."""
+    device RNG the way torch.nn.functional.gumbel_softmax does.
+
+    deterministic=True (learned.py:85-86): the edges are the hard sparsemax of the logits
+    (util.Spardmax: sparsemax of Martins & Astudillo 2016, straight through) - no noise is drawn,
+    `noise_fn` and `num_edge_samples` play no part, and the same state gives the same edges."""
 
     def __init__(self, input_size: int = 0, model: torch.nn.Sequential = None,
                  num_edge_samples: int = 5, deterministic: bool = False):
@@ -24,7 +28,7 @@ class LearnedEdge(torch.nn.Module):
         assert input_size or model, "Must specify either input_size or model"
         self.edge_network = model if model else self.build_edge_network(input_size)
         if deterministic:
-            self.sm = util.Spardmax()      # raises: dead at the reference HEAD as well
+            self.sm = util.Spardmax()      # what the deterministic kernels compute (csrc/learned_sparsemax.hip)
         self.ste = util.StraightThroughEstimator()
         self.noise_fn = None
 
@@ -46,14 +50,17 @@ class LearnedEdge(torch.nn.Module):
     def compute_new_adj(self, nodes, num_nodes, adj, B):
         """learned.py:53-113.  `adj` is rewritten in place (the caller hands over its own
         buffer, as DenseGCM does) and returned."""
+        det = self.deterministic
         cutoff = 1 / (1 + self.num_edge_samples)
-        if self.noise_fn is None:
-            # default edge network + device RNG: the whole selector is one autograd node
-            out = _ops.learned_edge_default(self.edge_network, nodes, adj, num_nodes, None, cutoff)
+        if det or self.noise_fn is None:
+            # default edge network (+ device RNG when sampling): the whole selector is one autograd node
+            out = _ops.learned_edge_default(self.edge_network, nodes, adj, num_nodes, None, cutoff, det)
             if out is not None:
                 return out
         pairs = _ops.learned_pairs(nodes, num_nodes)                  # [B, N, 2F]
         logits = _ops.edge_network_forward(self.edge_network, pairs).squeeze(-1)   # [B, N]
+        if det:
+            return _ops.learned_sparsemax_select_(adj, logits, num_nodes)
         if self.noise_fn is not None:
             noise = self.noise_fn(logits)
         else:

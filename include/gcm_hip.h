@@ -469,6 +469,11 @@ int gcm_learned_select_fwd(const float* logits, const float* noise, const int64_
 int gcm_learned_select_bwd(const float* g_adj, const float* soft, const int64_t* cur_idx,
                            float* g_logits, int B, int N, gcm_stream_t stream);
 
+/* learned.py:78-111 with the deterministic branch taken (LearnedEdge(deterministic=True)): hard sparsemax in place of
+ * the gumbel-softmax threshold (csrc/learned_sparsemax.hip).  Declared in gcm_hip_learned_det.h, which is part of this
+ * header and included here (inside the extern "C" block). */
+#include "gcm_hip_learned_det.h"
+
 /* ---- fused DenseGCM step for the canonical GNN (README.md:52-62, gcm.py:308-314) ------ */
 
 /* 1 when the fused kernels cover this shape (N <= 128, F <= 64, H1 <= 64, H2 <= 256 and the
