@@ -21,30 +21,11 @@
 // atomics: every sum runs in a fixed order.  Fi, H*C <= 128; any N.
 #include <cmath>
 
-#include "gcn_mm.h"
+#include "attn_bits.h"  // GT, k_gat_mask_bits
 
 namespace {
 
-constexpr int GT = 32;  // neighbour / row tile of the dense attention kernels
-
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-// bits[r, w] bit t: adj[r, 32 w + t] != 0 (the diagonal set when add_loop).  One wave per row.
-__global__ __launch_bounds__(256) void k_gat_mask_bits(const float* __restrict__ adj, unsigned* __restrict__ bits,
-                                                       int64_t rows, int N, int W, int add_loop) {
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const int i = (int)(row % N);
-  const float* a = adj + (size_t)row * N;
-  for (int j0 = 0; j0 < N; j0 += 64) {
-    const int j = j0 + lane;
-    const bool v = j < N && ((add_loop && j == i) || a[j] != 0.f);
-    const unsigned long long m = __ballot(v);
-    const int w = j0 / 32 + lane;
-    if (lane < 2 && w < W) bits[(size_t)row * W + w] = lane ? (unsigned)(m >> 32) : (unsigned)m;
-  }
-}
 
 // s_src[r,h] = <y[r,h,:], att_src[h]>, s_dst[r,h] likewise.  One thread per (r, h).
 __global__ void k_gat_scores(const float* __restrict__ y, const float* __restrict__ att_src,

@@ -26,6 +26,9 @@ _CONSTANTS.update(_abi.constants(_AGGR_HEADER))
 # and the section from gcm_hip_learned_det.h (LearnedEdge(deterministic=True): hard sparsemax selection)
 _LEARNED_DET_HEADER = _abi.header("gcm_hip_learned_det.h")
 LEARNED_DET_PROTOTYPES = _abi.prototypes(_LEARNED_DET_HEADER)
+# and the section from gcm_hip_transformer.h (TransformerConv / DenseTransformerConv)
+_TRANSFORMER_HEADER = _abi.header("gcm_hip_transformer.h")
+TRANSFORMER_PROTOTYPES = _abi.prototypes(_TRANSFORMER_HEADER)
 globals().update({name[4:]: value for name, value in _CONSTANTS.items()})   # GCM_ACT_TANH -> ACT_TANH, ...
 GCM_EUNSUPPORTED = _CONSTANTS["GCM_EUNSUPPORTED"]
 DIR = {d: _CONSTANTS["GCM_DIR_" + d.upper()] for d in ("forward", "backward", "both")}
@@ -63,6 +66,7 @@ def lib():
         handle = bind(ctypes.CDLL(os.environ.get("GCM_HIP_LIB") or _LIB_PATH))
         bind(handle, AGGR_PROTOTYPES)
         bind(handle, LEARNED_DET_PROTOTYPES)
+        bind(handle, TRANSFORMER_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

@@ -801,6 +801,111 @@ def csr_gatconv(x, w, att_src, att_dst, bias, graph, heads, concat, add_self_loo
 
 
 # ---------------------------------------------------------------------------
+# DenseTransformerConv / TransformerConv (PyG; csrc/transformerconv.hip)
+# ---------------------------------------------------------------------------
+def _transformer_dims(w_all, heads, concat, root):
+    """(H, C, D) from the stacked weight [3 H C + (D if root), Fi]: D = H C (concat) or C."""
+    H = heads
+    C = w_all.shape[0] // (3 * H + ((H if concat else 1) if root else 0))
+    D = H * C if concat else C
+    assert w_all.shape[0] == 3 * H * C + (D if root else 0), "w_all must stack [W_query; W_key; W_value; W_skip]"
+    return H, C, D
+
+
+class _DenseTransformerConv(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (only its nonzero pattern is read: no gradient), w_all [P,Fi] / b_all [P] the stacked
+    query, key, value (and skip) projections, w_beta [3 D] or None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, w_all, b_all, w_beta, heads, concat, root, add_loop):
+        x, adj, w_all, b_all = x.contiguous(), adj.contiguous(), w_all.contiguous(), b_all.contiguous()
+        w_beta = None if w_beta is None else w_beta.contiguous().view(-1)
+        _hip.on_device(x, adj, w_all, b_all, w_beta)
+        B, N, Fi = x.shape
+        H, C, D = _transformer_dims(w_all, heads, concat, root)
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert w_all.shape[1] == Fi and b_all.numel() == w_all.shape[0]
+        assert w_beta is None or w_beta.numel() == 3 * D
+        dims = (B, N, Fi, H, C, int(concat), int(root))
+        out = torch.empty(B, N, D, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_dense_transformerconv_fwd_workspace_bytes(*dims)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_transformerconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all), _hip.ptr(b_all),
+              _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, w_all, w_beta, saved)
+        ctx.dims = dims
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_all, w_beta, saved = ctx.saved_tensors
+        need_x, _, need_w, need_b, need_beta = ctx.needs_input_grad[:5]
+        g_out = g_out.contiguous()
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(w_all) if need_w else None
+        g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
+        g_beta = torch.empty_like(w_beta) if need_beta and w_beta is not None else None
+        ws_bytes = _hip.lib().gcm_dense_transformerconv_bwd_workspace_bytes(*ctx.dims)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_transformerconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w_all), _hip.ptr(w_beta),
+              _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_beta), _hip.ptr(ws), ws_bytes,
+              *ctx.dims, _hip.stream())
+        return g_x, None, g_w, g_b, g_beta, None, None, None, None
+
+
+def dense_transformerconv(x, adj, w_all, b_all, w_beta, heads, concat, root, add_loop):
+    """-> out [B,N,D]; w_beta is viewed flat [3 D] (its gradient comes back in its own shape)."""
+    return _DenseTransformerConv.apply(x, adj, w_all, b_all, w_beta, heads, concat, root, add_loop)
+
+
+class _CsrTransformerConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_all, b_all, w_beta, graph, heads, concat, root):
+        x, w_all, b_all = x.contiguous(), w_all.contiguous(), b_all.contiguous()
+        w_beta = None if w_beta is None else w_beta.contiguous().view(-1)
+        _hip.on_device(x, w_all, b_all, w_beta)
+        M, Fi = x.shape
+        H, C, D = _transformer_dims(w_all, heads, concat, root)
+        assert M == graph.M and w_all.shape[1] == Fi and b_all.numel() == w_all.shape[0]
+        assert w_beta is None or w_beta.numel() == 3 * D
+        dims = (M, graph.E, Fi, H, C, int(concat), int(root))
+        out = torch.empty(M, D, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_csr_transformerconv_fwd_workspace_bytes(*dims)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_transformerconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(w_all), _hip.ptr(b_all), _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims,
+              _hip.stream())
+        ctx.save_for_backward(x, w_all, w_beta, saved)
+        ctx.graph, ctx.dims = graph, dims
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_all, w_beta, saved = ctx.saved_tensors
+        graph = ctx.graph
+        need_x, need_w, need_b, need_beta = ctx.needs_input_grad[:4]
+        g_out = g_out.contiguous()
+        col_ptr = rows = perm = None
+        if graph.E > 0:
+            col_ptr, rows, perm = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(w_all) if need_w else None
+        g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
+        g_beta = torch.empty_like(w_beta) if need_beta and w_beta is not None else None
+        ws_bytes = _hip.lib().gcm_csr_transformerconv_bwd_workspace_bytes(*ctx.dims)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_transformerconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr),
+              _hip.ptr(graph.col), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_all),
+              _hip.ptr(w_beta), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_beta),
+              _hip.ptr(ws), ws_bytes, *ctx.dims, _hip.stream())
+        return g_x, g_w, g_b, g_beta, None, None, None, None
+
+
+def csr_transformerconv(x, w_all, b_all, w_beta, graph, heads, concat, root):
+    return _CsrTransformerConv.apply(x, w_all, b_all, w_beta, graph, heads, concat, root)
+
+
+# ---------------------------------------------------------------------------
 # mean / max aggregation: GraphConv(aggr=...), SAGEConv and their dense forms (csrc/aggrconv.hip)
 # ---------------------------------------------------------------------------
 AGGR = {"mean": _hip.AGGR_MEAN, "max": _hip.AGGR_MAX}

@@ -415,6 +415,117 @@ class GATv2Conv(torch.nn.Module):
         raise NotImplementedError("GATv2Conv is not implemented; gcm.nn has GATConv / DenseGATConv (GAT v1)")
 
 
+def _transformer_params(conv, in_channels, out_channels, heads, concat, beta, dropout, bias, root_weight):
+    if not isinstance(in_channels, int):
+        raise NotImplementedError("TransformerConv with a tuple in_channels (bipartite graphs) is not implemented")
+    if dropout < 0 or dropout > 1:
+        raise ValueError(f"dropout must be in [0, 1]; got {dropout}")
+    conv.in_channels, conv.out_channels, conv.heads, conv.concat = in_channels, out_channels, heads, concat
+    conv.root_weight, conv.beta, conv.dropout = root_weight, bool(beta and root_weight), dropout
+    width = heads * out_channels if concat else out_channels
+    conv.lin_key = torch.nn.Linear(in_channels, heads * out_channels)
+    conv.lin_query = torch.nn.Linear(in_channels, heads * out_channels)
+    conv.lin_value = torch.nn.Linear(in_channels, heads * out_channels)
+    conv.lin_skip = torch.nn.Linear(in_channels, width, bias=bias) if root_weight else None
+    conv.lin_beta = torch.nn.Linear(3 * width, 1, bias=False) if conv.beta else None
+
+
+def _transformer_reset(conv):
+    for lin in (conv.lin_key, conv.lin_query, conv.lin_value, conv.lin_skip, conv.lin_beta):
+        if lin is not None:
+            lin.reset_parameters()
+
+
+def _transformer_operands(conv):
+    """(w_all [P,F], b_all [P], w_beta [3 D] | None): the projections stacked [query; key; value; skip], so the
+    kernels make one pass over x and autograd hands each Linear its slice of the stacked gradient."""
+    lins = [conv.lin_query, conv.lin_key, conv.lin_value] + ([conv.lin_skip] if conv.root_weight else [])
+    w_all = torch.cat([lin.weight for lin in lins])
+    b_all = torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features) for lin in lins])
+    return w_all, b_all, (conv.lin_beta.weight.view(-1) if conv.beta else None)
+
+
+def _transformer_dropout(conv):
+    if conv.training and conv.dropout > 0:
+        raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
+
+
+class DenseTransformerConv(torch.nn.Module):
+    """The dense form of PyG's TransformerConv: adj[b,i,j] != 0 means i attends to j (only the pattern matters; the
+    diagonal counts as set when add_loop, which defaults to False so that dense and sparse agree on one edge set).
+    q, k, v = lin_query(x), lin_key(x), lin_value(x) viewed [B,N,H,C]; alpha = softmax_j(<q_i, k_j> / sqrt(C)) over
+    the pattern, o_i = sum_j alpha_ij v_j, heads concatenated (or averaged); with root_weight r = lin_skip(x) and out
+    = o + r, or with beta the gate b = sigmoid(lin_beta([o, r, o - r])), out = b r + (1 - b) o; * mask.  A row with
+    no neighbour aggregates nothing (o = 0).  Same parameters as TransformerConv: the state_dicts interchange.
+    Forward and backward are HIP kernels (csrc/transformerconv.hip); adj gets no gradient.  Attention dropout is
+    not implemented (dropout > 0 raises in training mode).  Not a DenseGraphConv: DenseGCM runs a stack of these
+    through its layered path."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True,
+                 root_weight=True):
+        super().__init__()
+        _transformer_params(self, in_channels, out_channels, heads, concat, beta, dropout, bias, root_weight)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _transformer_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=False):
+        _transformer_dropout(self)
+        x, adj = _dense_inputs(x, adj)
+        _hip.on_device(self.lin_query.weight)
+        w_all, b_all, w_beta = _transformer_operands(self)
+        out = _ops.dense_transformerconv(x, adj.detach(), w_all, b_all, w_beta, self.heads, self.concat,
+                                         self.root_weight, add_loop)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+
+
+class TransformerConv(torch.nn.Module):
+    """PyG's TransformerConv (flow source_to_target) without edge features: edge_index [2,E] = (source, sink), x
+    [M,F].  The edges are used as given: no loop is added or removed, duplicates are separate terms of the softmax,
+    which runs per destination over its incoming edges (a node with none: out = lin_skip(x), or 0 without
+    root_weight).  edge_attr is accepted and ignored, as PyG does without edge_dim.  Uses the `edge_index.gcm_graph`
+    index SparseGCM attaches; any other edge list is indexed here.  Forward and backward are HIP kernels
+    (csrc/transformerconv.hip).  Not implemented (NotImplementedError): attention dropout in training mode,
+    edge_dim, return_attention_weights, a tuple in_channels.  Not a GraphConv: SparseGCM runs a stack of these
+    through its generic path."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None,
+                 bias=True, root_weight=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("TransformerConv(edge_dim=...) is not implemented: edge features are not "
+                                      "attended to")
+        _transformer_params(self, in_channels, out_channels, heads, concat, beta, dropout, bias, root_weight)
+        self.edge_dim = edge_dim
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _transformer_reset(self)
+
+    def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None):
+        if return_attention_weights is not None:
+            raise NotImplementedError("TransformerConv(return_attention_weights=...) is not implemented")
+        _transformer_dropout(self)
+        _hip.on_device(self.lin_query.weight)     # a CPU module fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("TransformerConv does not take a masked GraphIndex (k-hop subgraphs reach it "
+                             "relabelled)")
+        w_all, b_all, w_beta = _transformer_operands(self)
+        return _ops.csr_transformerconv(x, w_all, b_all, w_beta, graph, self.heads, self.concat, self.root_weight)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).

@@ -424,6 +424,10 @@ int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_p
                         void* workspace, size_t workspace_bytes, int64_t M, int64_t E, int Fi, int H, int C,
                         int concat, int add_self_loops, float negative_slope, gcm_stream_t stream);
 
+/* ---- TransformerConv / DenseTransformerConv (PyG; csrc/transformerconv.hip) ----
+ * Declared in gcm_hip_transformer.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_transformer.h"
+
 /* ---- mean / max aggregation: GraphConv(aggr=...), SAGEConv (PyG; csrc/aggrconv.hip) ----
  * Declared in gcm_hip_aggr.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_aggr.h"
