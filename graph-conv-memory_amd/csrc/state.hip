@@ -175,6 +175,58 @@ extern "C" int gcm_state_advance_bwd(const float* g_nodes_out, const float* g_pl
 }
 
 // ---------------------------------------------------------------------------
+// masked clear of whole graphs (an episode's end): out[b] = mask[b] ? 0 : in[b]
+// ---------------------------------------------------------------------------
+// grid.x = chunks of a plane, grid.y = graph, grid.z = plane (0 nodes, 1 adj, 2 weights); V = f32x4 when every plane
+// of a graph is a whole number of 16-byte words at a 16-byte address, else float.  in == out: the graphs that keep
+// their state are not touched at all.
+template <typename V>
+__global__ __launch_bounds__(256) void k_state_reset(
+    const V* nodes_in, V* nodes_out, const V* adj_in, V* adj_out, const V* w_in, V* w_out, const int64_t* count_in,
+    int64_t* count_out, const uint8_t* __restrict__ mask, int len_nodes, int len_plane) {   // (in may alias out)
+  const int b = blockIdx.y, plane = blockIdx.z;
+  const bool clear = mask[b] != 0;
+  const V* src = plane == 0 ? nodes_in : (plane == 1 ? adj_in : w_in);
+  V* dst = plane == 0 ? nodes_out : (plane == 1 ? adj_out : w_out);
+  const int len = plane == 0 ? len_nodes : len_plane;
+  if (plane == 0 && blockIdx.x == 0 && threadIdx.x == 0 && count_out != nullptr && (clear || count_in != count_out))
+    count_out[b] = clear ? 0 : count_in[b];
+  if (dst == nullptr || (!clear && src == dst)) return;
+  src += (size_t)b * len;
+  dst += (size_t)b * len;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < len; e += gridDim.x * 256) {
+    V v = V(0.f);
+    if (!clear) v = src[e];               // (uniform over the block)
+    dst[e] = v;
+  }
+}
+
+extern "C" int gcm_state_reset(const float* nodes_in, float* nodes_out, const float* adj_in, float* adj_out,
+                               const float* weights_in, float* weights_out, const int64_t* count_in,
+                               int64_t* count_out, const uint8_t* mask, int B, int N, int F, gcm_stream_t stream) {
+  GCM_REQUIRE(nodes_in && nodes_out && adj_in && adj_out && mask && B > 0 && N > 0 && F > 0);
+  GCM_REQUIRE((weights_in == nullptr) == (weights_out == nullptr) && (count_in == nullptr) == (count_out == nullptr));
+  if (B > 65535 || (size_t)N * N > 2147483647u || (size_t)N * F > 2147483647u) return GCM_EUNSUPPORTED;
+  const int ln = N * F, lp = N * N;
+  const int n_planes = weights_in ? 3 : 2;
+  uintptr_t bits = (uintptr_t)nodes_in | (uintptr_t)nodes_out | (uintptr_t)adj_in | (uintptr_t)adj_out |
+                   (uintptr_t)weights_in | (uintptr_t)weights_out;
+  if ((bits & 15) == 0 && (ln & 3) == 0 && (lp & 3) == 0) {
+    const int most = (ln > lp ? ln : lp) / 4;
+    const int chunks = (most + 1023) / 1024 < 64 ? (most + 1023) / 1024 : 64;   // <= four 16-byte words a thread and trip
+    hipLaunchKernelGGL(k_state_reset<f32x4>, dim3(chunks, B, n_planes), dim3(256), 0, (hipStream_t)stream,
+                       (const f32x4*)nodes_in, (f32x4*)nodes_out, (const f32x4*)adj_in, (f32x4*)adj_out,
+                       (const f32x4*)weights_in, (f32x4*)weights_out, count_in, count_out, mask, ln / 4, lp / 4);
+    return gcm_launch_status();
+  }
+  const int most = ln > lp ? ln : lp;
+  const int chunks = (most + 1023) / 1024 < 64 ? (most + 1023) / 1024 : 64;
+  hipLaunchKernelGGL(k_state_reset<float>, dim3(chunks, B, n_planes), dim3(256), 0, (hipStream_t)stream, nodes_in,
+                     nodes_out, adj_in, adj_out, weights_in, weights_out, count_in, count_out, mask, ln, lp);
+  return gcm_launch_status();
+}
+
+// ---------------------------------------------------------------------------
 // belief row gather (gcm.py:309-318)
 // ---------------------------------------------------------------------------
 __global__ void k_gather_rows_fwd(const float* __restrict__ feats,

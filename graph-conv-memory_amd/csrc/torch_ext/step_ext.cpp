@@ -1843,9 +1843,12 @@ struct RowsRolloutNode : public torch::autograd::Node {
   std::string name() const override { return "GcmRowsRollout"; }
 };
 
-// -> (mx_all [T,B,H2], nodes [B,N,F], adj [B,N,N], count [B]) or None when the configuration has no such form
+// -> (mx_all [T,B,H2], nodes [B,N,F], adj [B,N,N], count [B]) or None when the configuration has no such form.
+// reset (bool [T,B] on the device, optional): graph b is emptied before step t where reset[t,b] - the forward of
+// csrc/rollout_reset.hip (episode starts in one launch, then the two time-parallel launches with the validity of a hop
+// decided per graph); same records, same node, same backward.
 pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, const at::Tensor& obs_,
-                                 const at::Tensor& flags) {
+                                 const at::Tensor& flags, const c10::optional<at::Tensor>& reset_) {
   StepCfg* cfg = reinterpret_cast<StepCfg*>(cfg_handle);
   TORCH_CHECK(cfg != nullptr && obs_.is_cuda() && packed.is_cuda() && flags.is_cuda(),
               "rows_rollout_tp: every tensor must live on a HIP device (no CPU fallback)");
@@ -1859,6 +1862,13 @@ pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, c
                       cfg->descs[0].mode == GCM_DIST_EUCLID_CROSSBATCH && !cfg->descs[0].bidirectional &&
                       cfg->descs[0].cur_rows == nullptr && !(cfg->has_bias & ~3) && T <= N && B <= 65535 &&
                       gcm_euclid_rollout_tp_supported((int)T, (int)B, N, F, H1, H2);
+  const bool with_reset = reset_.has_value() && reset_->defined();
+  if (with_reset) {
+    TORCH_CHECK(reset_->is_cuda() && reset_->scalar_type() == at::kBool && reset_->dim() == 2 && reset_->size(0) == T &&
+                    reset_->size(1) == B,
+                "rows_rollout_tp: reset must be a bool tensor [T, B] on the device");
+    if (euclid) return pybind11::none();   // (EuclideanEdge: the per-step loop)
+  }
   if (T > 65535 || (!euclid && !gcm_dense_rollout_tp_supported(cfg->descs.empty() ? nullptr : cfg->descs.data(),
                                                                (int)cfg->descs.size(), cfg->has_bias, (int)T, N, F, H1, H2)))
     return pybind11::none();
@@ -1868,7 +1878,8 @@ pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, c
   check(gcm_dense_rows_cached_layout((int)B, (int)Tc, F, H1, H2, lay), "gcm_dense_rows_cached_layout");
   const int64_t stride = need_bwd ? (int64_t)lay[0] : pad64(B * H2);
   at::Tensor records = at::empty({T * stride}, obs.options());
-  at::Tensor nodes = (T < N && !euclid) ? at::zeros({B, N, F}, obs.options()) : at::empty({B, N, F}, obs.options());
+  // (with resets a graph's final state may hold fewer than min(T, N) nodes: always zero-filled)
+  at::Tensor nodes = ((T < N || with_reset) && !euclid) ? at::zeros({B, N, F}, obs.options()) : at::empty({B, N, F}, obs.options());
   at::Tensor adj = euclid ? at::empty({B, N, N}, obs.options()) : at::zeros({B, N, N}, obs.options());
   at::Tensor count = at::empty({B}, obs.options().dtype(at::kLong));
   at::Tensor cH = at::empty({B, Tc, H1}, obs.options()), cA = at::empty({B, Tc, F}, obs.options()),
@@ -1884,6 +1895,20 @@ pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, c
                                     need_bwd ? 1 : 0, mx_all.data_ptr<float>(), reinterpret_cast<uint32_t*>(bits.data_ptr()),
                                     reinterpret_cast<uint32_t*>(flags.data_ptr()), (int)T, (int)B, N, (int)Tc, F, H1, H2, st),
           "gcm_euclid_rollout_tp_fwd");
+  } else if (with_reset) {
+    at::Tensor reset = reset_->contiguous();
+    at::Tensor start = at::empty({T, B}, obs.options().dtype(at::kInt));
+    check(gcm_episode_start(reinterpret_cast<const uint8_t*>(reset.data_ptr()), start.data_ptr<int32_t>(), (int)T, (int)B, st),
+          "gcm_episode_start");
+    check(gcm_dense_rollout_tp_reset_fwd(obs.data_ptr<float>(), start.data_ptr<int32_t>(),
+                                         cfg->descs.empty() ? nullptr : cfg->descs.data(), (int)cfg->descs.size(),
+                                         packed.data_ptr<float>(), cfg->has_bias, cfg->act1, cfg->act2,
+                                         nodes.data_ptr<float>(), adj.data_ptr<float>(), count.data_ptr<int64_t>(),
+                                         cH.data_ptr<float>(), cA.data_ptr<float>(), cX.data_ptr<float>(),
+                                         records.data_ptr<float>(), (size_t)stride, need_bwd ? 1 : 0,
+                                         mx_all.data_ptr<float>(), reinterpret_cast<uint32_t*>(flags.data_ptr()), (int)T,
+                                         (int)B, N, (int)Tc, F, H1, H2, st),
+          "gcm_dense_rollout_tp_reset_fwd");
   } else
   check(gcm_dense_rollout_tp_fwd(obs.data_ptr<float>(), cfg->descs.empty() ? nullptr : cfg->descs.data(),
                                  (int)cfg->descs.size(), packed.data_ptr<float>(), cfg->has_bias, cfg->act1, cfg->act2,
@@ -2761,7 +2786,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("forget", &LearnedFast::forget)
       .def("steps", [](LearnedFast& f) { return f.n_steps; });
   m.def("learned_rollout", &learned_rollout);
-  m.def("rows_rollout_tp", &rows_rollout_tp);
+  m.def("rows_rollout_tp", &rows_rollout_tp, pybind11::arg("cfg_handle"), pybind11::arg("packed"), pybind11::arg("obs"),
+        pybind11::arg("flags"), pybind11::arg("reset") = pybind11::none());
   pybind11::class_<SparseChain>(m, "SparseChain")
       .def(pybind11::init<>())
       .def("steps", [](SparseChain& c) { return c.steps; })

@@ -93,6 +93,62 @@ def state_advance(nodes, adj, weights, num_nodes, x, flags):
 
 
 # ---------------------------------------------------------------------------
+# masked clear of whole graphs (an episode's end): one launch, its own backward
+# ---------------------------------------------------------------------------
+def _state_reset_launch(nodes, nodes_out, adj, adj_out, weights, weights_out, count, count_out, mask):
+    B, N, F = nodes.shape
+    has_w = weights is not None and weights.numel() != 0
+    _hip.on_device(nodes, nodes_out, adj, adj_out, count, count_out, mask, *((weights, weights_out) if has_w else ()))
+    _call("gcm_state_reset", _hip.ptr(nodes), _hip.ptr(nodes_out), _hip.ptr(adj), _hip.ptr(adj_out),
+          _hip.ptr(weights) if has_w else None, _hip.ptr(weights_out) if has_w else None, _hip.ptr(count),
+          _hip.ptr(count_out), _hip.ptr(mask), B, N, F, _hip.stream())
+
+
+class _StateReset(torch.autograd.Function):
+    """(nodes, adj, weights, num_nodes) with the graphs of `mask` [B] (bool) emptied - gcm_state_reset.  inplace: the
+    given tensors are written (only their masked graphs) and returned, their version counters bumped (mark_dirty),
+    which is what tells the cached-step chains that the state is no longer the one they advanced."""
+
+    @staticmethod
+    def forward(ctx, nodes, adj, weights, num_nodes, mask, inplace):
+        has_w = weights.numel() != 0
+        if inplace:
+            outs = (nodes, adj, weights, num_nodes)
+        else:
+            nodes, adj, weights = nodes.contiguous(), adj.contiguous(), weights.contiguous()
+            num_nodes = num_nodes.contiguous()
+            outs = (_empty_like(nodes), _empty_like(adj), _empty_like(weights), torch.empty_like(num_nodes))
+        _state_reset_launch(nodes, outs[0], adj, outs[1], weights, outs[2], num_nodes, outs[3], mask)
+        if inplace:
+            ctx.mark_dirty(*((nodes, adj, weights, num_nodes) if has_w else (nodes, adj, num_nodes)))
+        ctx.save_for_backward(mask)
+        ctx.has_w = has_w
+        ctx.mark_non_differentiable(outs[3], *(o for o, need in zip(outs[:3], ctx.needs_input_grad) if not need))
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_nodes, g_adj, g_weights, _g_count):
+        (mask,) = ctx.saved_tensors
+        B = mask.shape[0]
+        if g_nodes is None:      # (one of the pair carries no gradient: the kernel takes both planes)
+            g_nodes = torch.zeros(B, g_adj.shape[1], 1, device=mask.device)
+        if g_adj is None:
+            g_adj = torch.zeros(B, g_nodes.shape[1], g_nodes.shape[1], device=mask.device)
+        g_nodes, g_adj = g_nodes.contiguous(), g_adj.contiguous()
+        g_weights = g_weights.contiguous() if ctx.has_w else None
+        gn, ga = torch.empty_like(g_nodes), torch.empty_like(g_adj)
+        gw = torch.empty_like(g_weights) if ctx.has_w else None
+        _state_reset_launch(g_nodes, gn, g_adj, ga, g_weights, gw, None, None, mask)
+        need = ctx.needs_input_grad
+        return (gn if need[0] else None, ga if need[1] else None, gw if need[2] and ctx.has_w else None, None, None,
+                None)
+
+
+def state_reset(nodes, adj, weights, num_nodes, mask, inplace=False):
+    return _StateReset.apply(nodes, adj, weights, num_nodes, mask, inplace)
+
+
+# ---------------------------------------------------------------------------
 # belief row gather + finite flag (gcm.py:309-318)
 # ---------------------------------------------------------------------------
 class _GatherRows(torch.autograd.Function):

@@ -778,7 +778,69 @@ class DenseGCM(torch.nn.Module):
             self._poll(flags)
         return mx, (nodes_out, adj_out, weights, num_nodes_next)
 
-    def rollout(self, obs, hidden=None, batch_first=False, truncate=True):
+    def _has_learned_edge(self):
+        from .edge_selectors.learned import LearnedEdge
+        return any(isinstance(m, LearnedEdge) for sel in (self.edge_selectors, self.aux_edge_selectors)
+                   if sel is not None for m in sel.modules())
+
+    def _check_reset(self, reset, T, B, what):
+        """Argument checks of a reset mask, before anything is launched."""
+        if not isinstance(reset, torch.Tensor) or reset.dtype != torch.bool:
+            raise TypeError(f"{what} must be a torch.bool tensor, got "
+                            f"{reset.dtype if isinstance(reset, torch.Tensor) else type(reset).__name__}")
+        want = (B,) if T is None else (T, B)
+        if tuple(reset.shape) != want:
+            raise ValueError(f"{what} must have shape {list(want)}, got {list(reset.shape)}")
+        if self._has_learned_edge():
+            # its adjacency carries the chain's gradient by step index (_gcm_lin): clearing some graphs of that tensor
+            # needs a design of its own
+            raise NotImplementedError("episode resets with a dense LearnedEdge selector are not implemented yet "
+                                      "(follow-up: per-graph resets of the LearnedEdge chain, whose adjacency carries "
+                                      "the gradient by step index); reset such a memory by starting a new rollout")
+
+    def reset_hidden(self, hidden, mask):
+        """The hidden state with the graphs of `mask` (bool [B], on the device or the CPU) emptied: node rows, adjacency,
+        weights if present, num_nodes = 0 - what an RL loop does to the memories of finished episodes, as one launch
+        (gcm_state_reset) and one autograd function (the gradient w.r.t. a cleared graph's incoming state is zero, the
+        others' the identity).  Functional by default: new tensors, the inputs untouched.  With donate_state=True the
+        given tensors are cleared in place and returned, and the running chain of cached steps ends (the next step
+        reads the state itself)."""
+        self._check_reset(mask, None, hidden[0].shape[0], "mask")
+        return self._apply_reset(hidden, mask)
+
+    def _apply_reset(self, hidden, mask):
+        nodes, adj, weights, num_nodes = hidden
+        if nodes.is_cuda and nodes.device.index != torch.cuda.current_device():
+            with torch.cuda.device(nodes.device):
+                return self._apply_reset(hidden, mask)
+        if mask.device != nodes.device:
+            mask = mask.to(nodes.device)
+        mask = mask.contiguous()
+        if self.donate_state:
+            if not (nodes.is_contiguous() and adj.is_contiguous() and num_nodes.is_contiguous()
+                    and weights.is_contiguous()):
+                raise ValueError("donate_state=True needs contiguous hidden-state tensors")
+            _ops.state_reset(nodes, adj, weights, num_nodes, mask, True)
+            # the cached-step chains read per-chain caches and the host's step count, not the state: the version
+            # counters moved (RowsFast::state_untouched), and the unchecked entries are dropped outright
+            self._fast = None
+            self._learned_chain = None
+            return hidden
+        n2, a2, w2, c2 = _ops.state_reset(nodes, adj, weights, num_nodes, mask, False)
+        return n2, a2, (w2 if weights.numel() else weights), c2
+
+    def _reset_plan(self, reset, device):
+        """(reset on the device [T, B], list of T bools: does step t clear a graph) - learned with ONE host read per
+        call (`reset.any(1)`), none at all when `reset` lives on the CPU."""
+        if reset.is_cuda:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DenseGCM.rollout(reset=...) on the per-step path reads which steps have a reset on "
+                                   "the host: inside a stream capture pass `reset` as a CPU tensor")
+            return reset.contiguous(), reset.any(1).tolist()
+        steps = reset.any(1).tolist()
+        return reset.contiguous().to(device), steps
+
+    def rollout(self, obs, hidden=None, batch_first=False, truncate=True, reset=None):
         """T memory steps at once: obs [T, B, feat] -> (beliefs [T, B, H], hidden after the
         last step); batch_first=True: obs [B, T, feat] -> beliefs [B, T, H] - the shape RLlib's wrapper holds
         (ray_gcm.py:186-209: `flat` [B, T, F] in, the stacked beliefs [B*T, H] out).  The VALUES (beliefs, hidden
@@ -794,14 +856,25 @@ class DenseGCM(torch.nn.Module):
         boundary, which is what RLlib's state passing does (ray_gcm.py:186-209 hands states over as detached
         batches).  A later call's loss then does not reach this call's edge selections through the returned
         adjacency, as it would across T forward() calls.  False: the chain of hidden states is kept across the call
-        boundary exactly as T forward() calls keep it (functional state, per-step kernels; slower)."""
+        boundary exactly as T forward() calls keep it (functional state, per-step kernels; slower).
+
+        reset (bool [T, B]; [B, T] with batch_first; on the device or the CPU): reset[t, b] empties graph b (node rows,
+        adjacency, weights, num_nodes = 0) BEFORE obs[t, b] is inserted - episodes that end inside the batch.  Values,
+        final hidden state and gradients are those of T forward() calls with reset_hidden() between them.  From
+        hidden = None with forward temporal hops the forward stays time-parallel (csrc/rollout_reset.hip: the validity
+        of a hop decided per graph, no host read); every other configuration runs the per-step loop with one masked
+        clear (gcm_state_reset) ahead of each step that has a reset.  None: no resets, the launches of before."""
         assert obs.dim() == 3 and obs.dtype == torch.float32
         if batch_first:
-            out, hidden = self.rollout(obs.transpose(0, 1), hidden, truncate=truncate)
+            if isinstance(reset, torch.Tensor) and reset.dim() == 2:
+                reset = reset.transpose(0, 1)
+            out, hidden = self.rollout(obs.transpose(0, 1), hidden, truncate=truncate, reset=reset)
             return out.transpose(0, 1), hidden
+        if reset is not None:
+            self._check_reset(reset, obs.shape[0], obs.shape[1], "reset")
         if obs.is_cuda and obs.device.index != torch.cuda.current_device():
             with torch.cuda.device(obs.device):
-                return self.rollout(obs, hidden, truncate=truncate)
+                return self.rollout(obs, hidden, truncate=truncate, reset=reset)
         if not truncate and torch.is_grad_enabled():
             from .edge_selectors.learned import LearnedEdge
             if any(isinstance(m, LearnedEdge) for sel in (self.edge_selectors, self.aux_edge_selectors)
@@ -834,8 +907,13 @@ class DenseGCM(torch.nn.Module):
                     and not (torch.is_grad_enabled() and obs.requires_grad)):
                 if cfg.cpp_handle():
                     flags = self._flag_word(obs.device)
-                    r = _ops._ext.module().rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True), obs,
-                                                           flags)
+                    if reset is None:
+                        r = _ops._ext.module().rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True),
+                                                               obs, flags)
+                    else:      # (copied to the device once if it came from the CPU: this path reads nothing back)
+                        r = _ops._ext.module().rows_rollout_tp(
+                            cfg.cpp_handle(), self._packed_params(cfg, head=True), obs, flags,
+                            reset.contiguous() if reset.is_cuda else reset.contiguous().to(obs.device))
                     if r is not None:
                         mx, nodes, adj, count = r
                         if self.finite_check == "sync":
@@ -843,12 +921,15 @@ class DenseGCM(torch.nn.Module):
                         elif self.finite_check == "deferred" and not torch.cuda.is_current_stream_capturing():
                             self.check_flags(block=False)
                             self._enqueue_flag_copy(flags)
-                        if obs.shape[0] > self.graph_size and self.finite_check != "off":
+                        # (with resets the kernel raises it: whether an episode outgrows the graph is not known here)
+                        if reset is None and obs.shape[0] > self.graph_size and self.finite_check != "off":
                             flags.bitwise_or_(_hip.FLAG_WRAPPED)     # gcm.py:264-266: the one-time overflow notice
                         return mx, (nodes, adj, torch.zeros(0, device=obs.device), count)
         if fresh:
             hidden = self.get_initial_hidden_state(obs[0])
         nodes, adj, weights, num_nodes = hidden
+        if reset is not None:             # the per-step kernels, a masked clear ahead of every step that has a reset
+            return self._rollout_loop(obs, hidden, fresh, self._reset_plan(reset, obs.device))
         cfg = self._fused_plan(nodes, adj, weights, obs.shape[-1])
         if cfg is not None and (cfg.learned_sel is not None or cfg.fold is not None):
             cfg = None                    # LearnedEdge / folded transforms: the per-step kernels, in a loop
@@ -899,7 +980,7 @@ class DenseGCM(torch.nn.Module):
             self._enqueue_flag_copy(flags)
         return mx, (nodes, adj, torch.zeros(0, device=obs.device), count)
 
-    def _rollout_loop(self, obs, hidden, fresh):
+    def _rollout_loop(self, obs, hidden, fresh, reset_plan=None):
         """rollout() as the loop of per-step calls.  The intermediate hidden states never leave this function, so -
         when no gradient flows through the state itself - the steps run on a state this call owns and advance it in
         place (the live-row / LearnedEdge kernels' donated form: no per-step copy of the 21 MB state), whatever the
@@ -916,6 +997,9 @@ class DenseGCM(torch.nn.Module):
         try:
             outs = []
             for t in range(obs.shape[0]):
+                # (a state this call owns is cleared in place, like the steps advance it; hidden = None: empty graphs)
+                if reset_plan is not None and reset_plan[1][t] and hidden is not None:
+                    hidden = self._apply_reset(hidden, reset_plan[0][t])
                 mx, hidden = self(obs[t], hidden)
                 outs.append(mx)
         finally:

@@ -1050,6 +1050,10 @@ int gcm_dense_rollout_tp_fwd(const float* obs, const gcm_selector_desc* selector
                              int record, float* mx_all, uint32_t* flags, int T, int B, int N, int Tc, int F, int H1,
                              int H2, gcm_stream_t stream);
 
+/* ---- per-graph episode resets: DenseGCM.rollout(reset=...) / DenseGCM.reset_hidden (csrc/rollout_reset.hip, state.hip) ----
+ * Declared in gcm_hip_reset.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_reset.h"
+
 /* ---- time-parallel DenseGCM rollout with EuclideanEdge (round 5; csrc/euclid_tp.hip) ----------------------------
  * DenseGCM.rollout(obs [T,B,F]) from EMPTY graphs with EuclideanEdge (edge_selectors/distance.py:18-49: the mean over
  * the B graphs' current nodes of the distance to a stored node, threshold max_distance; dist_param: the `learned`
