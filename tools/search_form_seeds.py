@@ -6,6 +6,11 @@ LearnedEdge decisions >= 1e-3 from flipping.  Prints the table (ReLU ratio, smal
 that are not 0, as the _SEEDS_NOT_0 dict of tests/_forms.py.
 
     python tools/search_form_seeds.py [case ...]
+
+--sparse: the same for tests/_sparse_forms.py (the SparseGCM cases of tests/test_sparse_forms_*.py; `learned` also
+asks for the same selected edges in float32 and float64).
+
+    python tools/search_form_seeds.py --sparse [case ...]
 """
 import math
 import os
@@ -23,6 +28,14 @@ import _forms as F  # noqa: E402
 
 def main(argv):
     torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))      # (as tests/conftest.py)
+    if "--sparse" in argv:      # the SparseGCM cases: same forms, margins and loop
+        import _sparse_forms
+        argv = [a for a in argv if a != "--sparse"]
+        return search(_sparse_forms, argv, "tests/_sparse_forms.py")
+    return search(F, argv, "tests/_forms.py")
+
+
+def search(F, argv, where):
     cases = argv or list(F.CASES)
     seeds, missing = {}, []
     print("%-9s %-15s %4s %9s %10s %12s %s" % ("case", "form", "seed", "pre-acts", "relu ratio", "sensitivity", "rejected"))
@@ -37,6 +50,7 @@ def main(argv):
             else:
                 missing.append((case, F.form_id(form)))
                 print("%-9s %-15s none in range(32)" % (case, F.form_id(form)))
+                sys.stdout.flush()
                 continue
             seeds[(case, F.form_id(form))] = seed
             relu = "-" if math.isinf(p.relu_ratio) else "%.1f" % p.relu_ratio
@@ -49,7 +63,7 @@ def main(argv):
             print("    (%r, %r): %d," % (case, fid, seed))
     print("}")
     if missing:
-        print("no seed for:", missing, "- shrink B of the case (tests/_forms.py CASES), do not lower the margin")
+        print("no seed for:", missing, "- shrink B of the case (%s CASES), do not lower the margin" % where)
         return 1
     return 0
 
