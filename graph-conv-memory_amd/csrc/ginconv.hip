@@ -1,0 +1,251 @@
+// GINConv / DenseGINConv (PyG): the aggregation and its gradients on gfx950.  The layer's `nn` is an arbitrary
+// module and stays in torch; what is here is
+//
+//   dense:  h = s x + adj @ x,  s = add_loop ? 1 + eps : 0      g_x = adj^T g_h + s g_h
+//           g_adj[b,i,j] = <g_h[b,i,:], x[b,j,:]>                g_eps = sum <g_h, x>
+//   sparse: h_i = (1 + eps) x_i + sum over the CSR row i of x[col]
+//           g_x[j] = (1 + eps) g_h[j] + sum over the CSC column j of g_h[rows]
+//
+// eps is read from its device pointer inside the kernels: no host read, so the calls stay HIP-graph capturable.
+// The dense contraction runs on v_mfma_f32_32x32x2_f32 in the tile layout of gcn_mm.h (128 rows x 32*NCT columns per
+// workgroup, K in tiles of 32 staged through LDS with zero padding, masked stores) with the self term added in the
+// epilogue: one launch for h, the same kernel with the adjacency read transposed for g_x.  g_adj is gcn_mm.h's
+// k_gcn_mm as it is.  g_eps: fp64 partial sums of fixed element ranges into the workspace, summed in a fixed order by
+// one workgroup - deterministic, no atomics.  F <= 128; any N.
+#include "gcn_mm.h"
+
+namespace {
+
+// C(b,i,:) = sum_k A(b,i,k) X(b,k,:) + s X(b,i,:);  A(b,i,k) = adj[b,i,k], or adj[b,k,i] when tr
+template <int NCT>
+__global__ __launch_bounds__(256) void k_gin_mm(const float* __restrict__ adj, const float* __restrict__ X,
+                                                const float* __restrict__ eps, float* __restrict__ C, int N, int F,
+                                                int tr, int add_loop) {
+  constexpr int NC = 32 * NCT;
+  __shared__ float sA[MB * (KT + 1)];  // [i][k]
+  __shared__ float sB[KT * (NC + 1)];  // [k][j]
+  const int b = blockIdx.z;
+  const int i0 = blockIdx.x * MB;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  const float* Ab = adj + (size_t)b * N * N;
+  const float* Xb = X + (size_t)b * N * F;
+  float* Cb = C + (size_t)b * N * F;
+
+  f32x16 acc[NCT];
+#pragma unroll
+  for (int c = 0; c < NCT; ++c)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+
+  for (int k0 = 0; k0 < N; k0 += KT) {
+    for (int e = threadIdx.x; e < MB * KT; e += 256) {  // the fast index of the global read is the fast thread index
+      const int r = tr ? e % MB : e / KT, k = tr ? e / MB : e % KT;
+      const int gi = i0 + r, gk = k0 + k;
+      float v = 0.f;
+      if (gi < N && gk < N) v = tr ? Ab[(size_t)gk * N + gi] : Ab[(size_t)gi * N + gk];
+      sA[r * (KT + 1) + k] = v;
+    }
+    for (int e = threadIdx.x; e < KT * NC; e += 256) {
+      const int k = e / NC, j = e % NC;
+      const int gk = k0 + k;
+      sB[k * (NC + 1) + j] = (gk < N && j < F) ? Xb[(size_t)gk * F + j] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NCT; ++c)
+      mma32(acc[c], sA + wave * 32 * (KT + 1), KT + 1, 1, sB + c * 32, NC + 1, 1, KT, li, lh);
+    __syncthreads();
+  }
+
+  const float s = add_loop ? 1.f + eps[0] : 0.f;
+#pragma unroll
+  for (int c = 0; c < NCT; ++c) {
+    const int j = c * 32 + li;
+    if (j >= F) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = i0 + wave * 32 + acc_row(r, lh);
+      if (i >= N) continue;
+      const size_t off = (size_t)i * F + j;
+      float v = acc[c][r];
+      if (add_loop) v = fmaf(s, Xb[off], v);
+      Cb[off] = v;
+    }
+  }
+}
+
+int launch_gin_mm(const float* adj, const float* X, const float* eps, float* C, int B, int N, int F, int tr,
+                  int add_loop, hipStream_t s) {
+  const dim3 grid((N + MB - 1) / MB, 1, B);
+  switch ((F + 31) / 32) {
+    case 1: hipLaunchKernelGGL(k_gin_mm<1>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
+    case 2: hipLaunchKernelGGL(k_gin_mm<2>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
+    case 3: hipLaunchKernelGGL(k_gin_mm<3>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
+    default: hipLaunchKernelGGL(k_gin_mm<4>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
+  }
+  return gcm_launch_status();
+}
+
+// out[i,:] = (1 + eps) src[i,:] + sum over ptr[i] <= k < ptr[i+1] of src[idx[k],:]   (one thread per element; the
+// destination CSR with x for the forward, the CSC by source with g_h for the backward; ptr NULL: no entries)
+__global__ __launch_bounds__(256) void k_gin_gather(const float* __restrict__ src, const int64_t* __restrict__ ptr,
+                                                    const int64_t* __restrict__ idx, const float* __restrict__ eps,
+                                                    float* __restrict__ out, int64_t M, int F) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= M * F) return;
+  const int64_t i = t / F;
+  const int f = (int)(t - i * F);
+  float a = 0.f;
+  if (ptr) {
+    const int64_t k1 = ptr[i + 1];
+    for (int64_t k = ptr[i]; k < k1; ++k) a += src[(size_t)idx[k] * F + f];
+  }
+  out[t] = fmaf(1.f + eps[0], src[t], a);
+}
+
+// g_eps, pass 1: part[blk] = sum of a[e] b[e] over the block's element range [blk * chunk, (blk + 1) * chunk), in
+// fp64 (every product exact), lanes and waves combined in a fixed order
+constexpr int DOT_BLOCKS = 1024;  // at most; chunk a multiple of 256
+
+__global__ __launch_bounds__(256) void k_gin_dot_parts(const float* __restrict__ a, const float* __restrict__ b,
+                                                       int64_t L, int64_t chunk, double* __restrict__ part) {
+  __shared__ double sp[256];
+  const int64_t e0 = (int64_t)blockIdx.x * chunk;
+  const int64_t e1 = min(L, e0 + chunk);
+  double s = 0.0;
+  for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) s += (double)a[e] * (double)b[e];
+  sp[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sp[threadIdx.x] += sp[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = sp[0];
+}
+
+// pass 2 (one workgroup): out[0] = sum of the n partials in a fixed order
+__global__ __launch_bounds__(256) void k_gin_dot_final(const double* __restrict__ part, int n,
+                                                       float* __restrict__ out) {
+  __shared__ double sp[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+  sp[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sp[threadIdx.x] += sp[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)sp[0];
+}
+
+void dot_plan(int64_t L, int* nblocks, int64_t* chunk) {
+  int64_t c = (L + DOT_BLOCKS - 1) / DOT_BLOCKS;
+  c = std::max<int64_t>((c + 255) / 256 * 256, 4096);
+  *chunk = c;
+  *nblocks = (int)((L + c - 1) / c);
+}
+
+size_t dot_ws_bytes(int64_t L) {
+  int n;
+  int64_t c;
+  dot_plan(L, &n, &c);
+  return align256((size_t)n * sizeof(double));
+}
+
+int dot_sum(const float* a, const float* b, int64_t L, float* out, void* workspace, hipStream_t s) {
+  int n;
+  int64_t c;
+  dot_plan(L, &n, &c);
+  double* part = (double*)workspace;
+  hipLaunchKernelGGL(k_gin_dot_parts, dim3(n), dim3(256), 0, s, a, b, L, c, part);
+  int rc = gcm_launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gin_dot_final, dim3(1), dim3(256), 0, s, part, n, out);
+  return gcm_launch_status();
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// C ABI: DenseGINConv
+// ---------------------------------------------------------------------------
+extern "C" int gcm_dense_gin_fwd(const float* x, const float* adj, const float* eps, float* h, int B, int N, int F,
+                                 int add_loop, gcm_stream_t stream) {
+  GCM_REQUIRE(x && adj && eps && h);
+  GCM_REQUIRE(B > 0 && N > 0 && F > 0);
+  if (F > 128 || B > 65535 || (int64_t)B * N > (1 << 30)) return GCM_EUNSUPPORTED;
+  return launch_gin_mm(adj, x, eps, h, B, N, F, 0, add_loop, (hipStream_t)stream);
+}
+
+extern "C" size_t gcm_dense_gin_bwd_workspace_bytes(int B, int N, int F) {
+  if (B <= 0 || N <= 0 || F <= 0) return 0;
+  return dot_ws_bytes((int64_t)B * N * F);
+}
+
+extern "C" int gcm_dense_gin_bwd(const float* g_h, const float* x, const float* adj, const float* eps, float* g_x,
+                                 float* g_adj, float* g_eps, void* workspace, size_t workspace_bytes, int B, int N,
+                                 int F, int add_loop, gcm_stream_t stream) {
+  GCM_REQUIRE(g_h && x && adj && eps && workspace);
+  GCM_REQUIRE(B > 0 && N > 0 && F > 0);
+  if (F > 128 || B > 65535 || (int64_t)B * N > (1 << 30)) return GCM_EUNSUPPORTED;
+  const int64_t L = (int64_t)B * N * F;
+  GCM_REQUIRE(workspace_bytes >= dot_ws_bytes(L));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (g_x && (rc = launch_gin_mm(adj, g_h, eps, g_x, B, N, F, 1, add_loop, s))) return rc;
+  if (g_adj) {  // g_adj_ij = <g_h_i, x_j>
+    MmArgs p = mm_args();
+    p.A = g_h, p.a_bs = (int64_t)N * F, p.a_is = F, p.a_ks = 1;
+    p.B = x, p.b_bs = (int64_t)N * F, p.b_ks = 1, p.b_js = F;
+    p.C = g_adj, p.c_bs = (int64_t)N * N, p.c_is = N, p.c_js = 1;
+    p.M = N, p.N = N, p.K = F, p.batch = B;
+    if ((rc = launch_mm(p, 1, s))) return rc;
+  }
+  if (g_eps) {
+    if (add_loop) {
+      if ((rc = dot_sum(g_h, x, L, g_eps, workspace, s))) return rc;
+    } else {  // eps is not used: the sum of no partials
+      hipLaunchKernelGGL(k_gin_dot_final, dim3(1), dim3(256), 0, s, (const double*)workspace, 0, g_eps);
+      if ((rc = gcm_launch_status())) return rc;
+    }
+  }
+  return GCM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// C ABI: GINConv
+// ---------------------------------------------------------------------------
+extern "C" int gcm_csr_gin_fwd(const float* x, const int64_t* row_ptr, const int64_t* col, const float* eps, float* h,
+                               int64_t M, int64_t E, int F, gcm_stream_t stream) {
+  GCM_REQUIRE(x && row_ptr && eps && h);
+  GCM_REQUIRE(M > 0 && E >= 0 && F > 0);
+  GCM_REQUIRE(E == 0 || col);
+  if (F > 128 || M > (1 << 30)) return GCM_EUNSUPPORTED;
+  hipLaunchKernelGGL(k_gin_gather, dim3(blocks(M * F, 256)), dim3(256), 0, (hipStream_t)stream, x,
+                     E > 0 ? row_ptr : nullptr, col, eps, h, M, F);
+  return gcm_launch_status();
+}
+
+extern "C" size_t gcm_csr_gin_bwd_workspace_bytes(int64_t M, int64_t E, int F) {
+  if (M <= 0 || E < 0 || F <= 0) return 0;
+  return dot_ws_bytes(M * F);
+}
+
+extern "C" int gcm_csr_gin_bwd(const float* g_h, const float* x, const float* eps, const int64_t* col_ptr,
+                               const int64_t* rows, float* g_x, float* g_eps, void* workspace, size_t workspace_bytes,
+                               int64_t M, int64_t E, int F, gcm_stream_t stream) {
+  GCM_REQUIRE(g_h && eps && workspace);
+  GCM_REQUIRE(M > 0 && E >= 0 && F > 0);
+  GCM_REQUIRE(!g_eps || x);
+  GCM_REQUIRE(E == 0 || !g_x || (col_ptr && rows));
+  if (F > 128 || M > (1 << 30)) return GCM_EUNSUPPORTED;
+  GCM_REQUIRE(workspace_bytes >= dot_ws_bytes(M * F));
+  hipStream_t s = (hipStream_t)stream;
+  if (g_x) {
+    hipLaunchKernelGGL(k_gin_gather, dim3(blocks(M * F, 256)), dim3(256), 0, s, g_h, E > 0 ? col_ptr : nullptr, rows,
+                       eps, g_x, M, F);
+    const int rc = gcm_launch_status();
+    if (rc) return rc;
+  }
+  return g_eps ? dot_sum(g_h, x, M * F, g_eps, workspace, s) : GCM_OK;
+}

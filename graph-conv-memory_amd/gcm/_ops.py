@@ -738,6 +738,89 @@ def csr_gcnconv(x, w_edge, w, bias, graph, normalize, add_self_loops, fill):
 
 
 # ---------------------------------------------------------------------------
+# DenseGINConv / GINConv (PyG; csrc/ginconv.hip): the aggregation alone, the layer's `nn` stays in torch
+# ---------------------------------------------------------------------------
+class _DenseGINAggregate(torch.autograd.Function):
+    """h = s x + adj @ x, s = 1 + eps if add_loop else 0; x [B,N,F], adj [B,N,N], eps [1] (read on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, adj, eps, add_loop):
+        x, adj, eps = x.contiguous(), adj.contiguous(), eps.contiguous()
+        _hip.on_device(x, adj, eps)
+        B, N, F = x.shape
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert eps.numel() == 1 and eps.dtype == _f32
+        h = torch.empty(B, N, F, device=x.device, dtype=_f32)
+        _call("gcm_dense_gin_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(eps), _hip.ptr(h), B, N, F, int(add_loop),
+              _hip.stream())
+        ctx.save_for_backward(x, adj, eps)
+        ctx.add_loop = int(add_loop)
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        x, adj, eps = ctx.saved_tensors
+        B, N, F = x.shape
+        need_x, need_adj, need_eps, _ = ctx.needs_input_grad
+        g_h = g_h.contiguous()
+        dev = x.device
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_eps = torch.empty_like(eps) if need_eps else None
+        ws_bytes = _hip.lib().gcm_dense_gin_bwd_workspace_bytes(B, N, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_dense_gin_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(eps), _hip.ptr(g_x),
+              _hip.ptr(g_adj), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, B, N, F, ctx.add_loop, _hip.stream())
+        return g_x, g_adj, g_eps, None
+
+
+def dense_gin_aggregate(x, adj, eps, add_loop):
+    return _DenseGINAggregate.apply(x, adj, eps, add_loop)
+
+
+class _CsrGINAggregate(torch.autograd.Function):
+    """h_i = (1 + eps) x_i + sum over the in-edges of i of x_source; x [M,F], eps [1] (read on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, eps, graph):
+        x, eps = x.contiguous(), eps.contiguous()
+        _hip.on_device(x, eps)
+        M, F = x.shape
+        assert M == graph.M
+        assert eps.numel() == 1 and eps.dtype == _f32
+        h = torch.empty(M, F, device=x.device, dtype=_f32)
+        _call("gcm_csr_gin_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(eps),
+              _hip.ptr(h), M, graph.E, F, _hip.stream())
+        ctx.save_for_backward(x, eps)
+        ctx.graph = graph
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        x, eps = ctx.saved_tensors
+        graph = ctx.graph
+        M, F = x.shape
+        E = graph.E
+        need_x, need_eps, _ = ctx.needs_input_grad
+        g_h = g_h.contiguous()
+        dev = x.device
+        col_ptr = rows = None
+        if need_x and E > 0:
+            col_ptr, rows, _ = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_eps = torch.empty_like(eps) if need_eps else None
+        ws_bytes = _hip.lib().gcm_csr_gin_bwd_workspace_bytes(M, E, F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_csr_gin_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(eps), _hip.ptr(col_ptr), _hip.ptr(rows),
+              _hip.ptr(g_x), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, M, E, F, _hip.stream())
+        return g_x, g_eps, None
+
+
+def csr_gin_aggregate(x, eps, graph):
+    return _CsrGINAggregate.apply(x, eps, graph)
+
+
+# ---------------------------------------------------------------------------
 # DenseGATConv / GATConv (PyG, GAT v1; csrc/gatconv.hip)
 # ---------------------------------------------------------------------------
 class _DenseGATConv(torch.autograd.Function):

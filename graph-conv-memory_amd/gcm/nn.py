@@ -301,6 +301,82 @@ class GCNConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
 
 
+def _gin_init(conv, nn, eps, train_eps):
+    conv.nn, conv.initial_eps = nn, float(eps)
+    if train_eps:
+        conv.eps = torch.nn.Parameter(torch.empty(1))
+    else:
+        conv.register_buffer("eps", torch.empty(1))
+    conv.reset_parameters()
+
+
+def _gin_reset(module):
+    """PyG's `reset`: reset_parameters() of every submodule that has one."""
+    if hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+    else:
+        for child in module.children():
+            _gin_reset(child)
+
+
+class DenseGINConv(torch.nn.Module):
+    """PyG's DenseGINConv: h = adj @ x, plus (1 + eps) x when add_loop; out = nn(h), times the mask.  adj [B,N,N]
+    float (adj[b,i,j]: i aggregates from j): its values are weights and get a gradient, and its diagonal is an
+    ordinary entry that add_loop does not overwrite.  x [B,N,F], F <= 128.  The aggregation and its gradients
+    (x, adj, eps) are HIP kernels (csrc/ginconv.hip) that read eps on the device; `nn` is any module and runs under
+    torch autograd (pass gcm.nn.SkinnyLinear layers for no library GEMM).  `eps` [1] is a Parameter when train_eps,
+    else a buffer; state_dict keys `eps`, `nn.*`, shared with GINConv.  Not a DenseGraphConv: DenseGCM runs a GIN
+    stack through its layered path."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False):
+        super().__init__()
+        _gin_init(self, nn, eps, train_eps)
+
+    def reset_parameters(self):
+        _gin_reset(self.nn)
+        self.eps.data.fill_(self.initial_eps)
+
+    def forward(self, x, adj, mask=None, add_loop=True):
+        x, adj = _dense_inputs(x, adj)
+        h = _ops.dense_gin_aggregate(x, adj, self.eps, add_loop)
+        out = self.nn(h)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(nn={self.nn})"
+
+
+class GINConv(torch.nn.Module):
+    """PyG's GINConv (flow source_to_target): h_i = (1 + eps) x_i + sum over the edges j -> i of x_j, out = nn(h);
+    edge_index [2,E] = (source, sink), x [M,F], F <= 128.  The edges are used as given: no self-loop is added or
+    removed, an i -> i edge is an ordinary term, duplicates count once each; there are no edge weights.  The CSR
+    aggregation and its gradients (x, eps) are HIP kernels (csrc/ginconv.hip); `nn` runs under torch autograd.  Uses
+    the `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed here.  Parameters as
+    DenseGINConv.  Not a GraphConv: SparseGCM runs a GIN stack through its generic path."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False):
+        super().__init__()
+        _gin_init(self, nn, eps, train_eps)
+
+    def reset_parameters(self):
+        _gin_reset(self.nn)
+        self.eps.data.fill_(self.initial_eps)
+
+    def forward(self, x, edge_index):
+        _hip.on_device(x, self.eps)     # a CPU call fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("GINConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        return self.nn(_ops.csr_gin_aggregate(x, self.eps, graph))
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(nn={self.nn})"
+
+
 def _gat_check(dropout, edge_dim=None):
     """Widths beyond the kernels' (in_channels or heads * out_channels > 128) raise at the first call."""
     if dropout < 0 or dropout > 1:
