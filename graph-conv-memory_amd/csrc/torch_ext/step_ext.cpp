@@ -53,6 +53,7 @@ struct StepCfg {
   int act1, act2, has_bias, N, F, H1, H2;
   int cached_flags = 0;   // extra has_bias bits of the cached step only (GCM_STEP_TWO_LAUNCH: the A/B of tests / tools)
   bool col_cache = true;  // chains whose selectors write column cur take gcm_dense_rows_step_colcache (A/B switch)
+  bool hops_bptt = true;  // forward-hop cached chains take gcm_dense_rows_bptt_cached_hops in their backward (A/B switch)
   int64_t P;
   bool has_distance = false;
   at::Tensor ws;   // scratch of the distance selectors
@@ -267,9 +268,12 @@ struct RowsChainNode : public torch::autograd::Node {
     int out_nodes = -1;         // dx: ... and the returned node matrix
     int edge_x = -1;            // dx: the next edge that leads to this step's observation (-1: no gradient)
     bool cached = false;        // a cached step (rows_cached.hip): the live rows are in the chain's caches
+    int cur = -1;               // ... and, hop_rows set, the row it wrote: known on the host.  hop_rows: ANY cached step of a
+    bool hop_rows = false;      // chain without a distance selector (lean or not: cur_host = the chain's step count in both)
   };
   at::Tensor cH, cA, cX;        // the caches of the chain's cached steps
   bool many_rows = false;       // a DenseEdge selector: every row <= cur is live (GCM_BPTT_MANY_ROWS)
+  bool hops_bptt = true;        // StepCfg::hops_bptt when the chain was armed
   std::vector<gcm_selector_desc> descs;   // ... and the selectors their live rows follow from (dx of cached steps)
   std::vector<Rec> recs;   // the recorded steps, in chain order
   at::Tensor packed;       // the packed parameter vector, detached (the kernel re-reads the weights)
@@ -382,7 +386,18 @@ struct RowsChainNode : public torch::autograd::Node {
       int64_t B, sb, sh;
       bool cached;
       std::vector<const float*> sv, gm;
+      std::vector<uint8_t> cur;
     };
+    // the GEMM-form backward (gcm_dense_rows_bptt_cached_hops): only while EVERY step of the chain is a cached step with
+    // a host-known row - a chain that left that case mid-way keeps the kernel that reads the records' live lists
+    // (GCM_BPTT_PER_ITEM=1, the A/B of the record walk's two kernels, asks for the record walk: it wins)
+    static const bool want_walk = std::getenv("GCM_BPTT_PER_ITEM") && std::getenv("GCM_BPTT_PER_ITEM")[0] == '1';
+    bool hop_chain = hops_bptt && !want_walk && !recs.empty() && cH.defined();
+    int rows_written = 0;
+    for (const Rec& r : recs) {
+      hop_chain = hop_chain && r.cached && r.hop_rows && r.cur >= 0 && r.cur < 128;
+      rows_written = std::max(rows_written, r.cur + 1);
+    }
     std::vector<Group> groups;
     std::vector<at::Tensor> keep;
     for (size_t k = 0; k < recs.size(); ++k) {
@@ -403,11 +418,12 @@ struct RowsChainNode : public torch::autograd::Node {
       for (auto& c : groups)
         if (c.B == B && c.sb == sb && c.sh == sh && c.cached == r.cached) grp = &c;
       if (!grp) {
-        groups.push_back({B, sb, sh, r.cached, {}, {}});
+        groups.push_back({B, sb, sh, r.cached, {}, {}, {}});
         grp = &groups.back();
       }
       grp->sv.push_back(r.buf.data_ptr<float>());
       grp->gm.push_back(g.data_ptr<float>());
+      grp->cur.push_back((uint8_t)(r.cur & 0xff));
     }
     const gcm_stream_t stream =
         reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(packed.get_device()).stream());
@@ -416,7 +432,10 @@ struct RowsChainNode : public torch::autograd::Node {
     at::Tensor prev;
     for (auto& c : groups) {
       const int n = (int)c.sv.size();
-      const size_t ws_bytes = gcm_dense_rows_bptt_workspace_bytes(n, (int)c.B, F, H1, H2);
+      const bool hops = c.cached && hop_chain && c.B == cH.size(0);
+      // (the GEMM form writes one slab per graph)
+      const size_t ws_bytes = std::max(gcm_dense_rows_bptt_workspace_bytes(n, (int)c.B, F, H1, H2),
+                                       hops ? sizeof(float) * (size_t)P * (size_t)c.B : (size_t)0);
       at::Tensor ws = at::empty({(int64_t)ws_bytes}, packed.options().dtype(at::kByte));
       // the kernel writes the first P floats; constant sections behind them get a zero gradient
       at::Tensor res = packed.numel() > P ? at::zeros({packed.numel()}, packed.options())
@@ -425,7 +444,18 @@ struct RowsChainNode : public torch::autograd::Node {
       //  C ABI, read from the environment by this host module once)
       static const int per_item = (std::getenv("GCM_BPTT_PER_ITEM") && std::getenv("GCM_BPTT_PER_ITEM")[0] == '1')
                                       ? GCM_STEP_FOUR_WAVES : 0;
-      if (c.cached)
+      int hops_rc = GCM_EUNSUPPORTED;
+      if (hops)
+        hops_rc = gcm_dense_rows_bptt_cached_hops(c.sv.data(), c.gm.data(), n, (long)c.sb, (long)c.sh,
+                                                  packed.data_ptr<float>(), has_bias, act1, act2, cX.data_ptr<float>(),
+                                                  cH.data_ptr<float>(), cA.data_ptr<float>(), c.cur.data(),
+                                                  descs.empty() ? nullptr : descs.data(), (int)descs.size(), rows_written,
+                                                  prev.defined() ? prev.data_ptr<float>() : nullptr,
+                                                  res.data_ptr<float>(), ws.data_ptr(), ws_bytes, (int)c.B, N, F, H1, H2,
+                                                  stream);
+      if (hops_rc != GCM_EUNSUPPORTED)   // (unsupported: a case the GEMM form has no kernel for - the record walk below)
+        check(hops_rc, "gcm_dense_rows_bptt_cached_hops");
+      else if (c.cached)
         check(gcm_dense_rows_bptt_cached(c.sv.data(), c.gm.data(), n, (long)c.sb, (long)c.sh, packed.data_ptr<float>(),
                                          has_bias | per_item, act1, act2, cX.data_ptr<float>(), cH.data_ptr<float>(),
                                          cA.data_ptr<float>(), prev.defined() ? prev.data_ptr<float>() : nullptr,
@@ -750,6 +780,7 @@ struct RowsFast {
                 ((cfg->has_bias & GCM_GNN_HAS_DEG_TERM) ? cfg->H1 : 0);
       TORCH_CHECK(packed.numel() >= node->P, "rows step: packed parameter vector too short");
       for (const auto& d : cfg->descs) node->many_rows = node->many_rows || d.kind == GCM_SEL_DENSE;
+      node->hops_bptt = cfg->hops_bptt;
       node->set_next_edges(torch::autograd::collect_next_edges(packed));
       if (dx_ == 1) {
         dx_mode = true;
@@ -997,6 +1028,8 @@ struct RowsFast {
       const c10::VariableVersion& vc = mx.unsafeGetTensorImpl()->version_counter();
       RowsChainNode::Rec r{buf, vc, vc.current_version()};
       r.cached = true;
+      r.cur = (int)cached_steps;
+      r.hop_rows = !cfg->has_distance;
       if (dx_kind == 1) r.edge_x = node->take_x_edge(obs);
       r.out_mx = (int)node->num_inputs();
       torch::autograd::create_gradient_edge(mx, node);
@@ -1808,6 +1841,10 @@ struct RowsRolloutNode : public torch::autograd::Node {
   int64_t T = 0, B = 0, Tc = 0, stride = 0;
   int F = 0, H1 = 0, H2 = 0, has_bias = 0, act1 = 0, act2 = 0;
   bool released = false;
+  // from empty graphs, no resets, T <= N <= 128 (every row below T written by step t = row t, every hop a row of the
+  // same graph): gcm_dense_rows_bptt_cached_hops with the trivial table
+  bool hop_rows = false;
+  std::vector<gcm_selector_desc> descs;
   variable_list apply(variable_list&& grads) override {
     variable_list out(1);
     TORCH_CHECK(!released, "Trying to backward through a DenseGCM.rollout a second time (its records were freed); "
@@ -1824,10 +1861,24 @@ struct RowsRolloutNode : public torch::autograd::Node {
     }
     const gcm_stream_t stream =
         reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(packed.get_device()).stream());
-    const size_t ws_bytes = gcm_dense_rows_bptt_workspace_bytes((int)T, (int)B, F, H1, H2);
-    at::Tensor ws = at::empty({(int64_t)ws_bytes}, packed.options().dtype(at::kByte));
     const int64_t P = (int64_t)gcm_dense_gnn2_param_count(F, H1, H2);
+    const size_t ws_bytes = std::max(gcm_dense_rows_bptt_workspace_bytes((int)T, (int)B, F, H1, H2),
+                                     hop_rows ? sizeof(float) * (size_t)P * (size_t)B : (size_t)0);
+    at::Tensor ws = at::empty({(int64_t)ws_bytes}, packed.options().dtype(at::kByte));
     at::Tensor res = packed.numel() > P ? at::zeros({packed.numel()}, packed.options()) : at::empty({P}, packed.options());
+    int hops_rc = GCM_EUNSUPPORTED;
+    if (hop_rows) {
+      std::vector<uint8_t> cur((size_t)T);
+      for (int64_t t = 0; t < T; ++t) cur[t] = (uint8_t)t;
+      hops_rc = gcm_dense_rows_bptt_cached_hops(sv.data(), gm.data(), (int)T, (long)g.stride(1), (long)g.stride(2),
+                                                packed.data_ptr<float>(), has_bias, act1, act2, cX.data_ptr<float>(),
+                                                cH.data_ptr<float>(), cA.data_ptr<float>(), cur.data(),
+                                                descs.empty() ? nullptr : descs.data(), (int)descs.size(), (int)T, nullptr,
+                                                res.data_ptr<float>(), ws.data_ptr(), ws_bytes, (int)B, (int)Tc, F, H1, H2,
+                                                stream);
+    }
+    if (hops_rc != GCM_EUNSUPPORTED) check(hops_rc, "gcm_dense_rows_bptt_cached_hops");
+    else
     check(gcm_dense_rows_bptt_cached(sv.data(), gm.data(), (int)T, (long)g.stride(1), (long)g.stride(2),
                                      packed.data_ptr<float>(), has_bias, act1, act2, cX.data_ptr<float>(),
                                      cH.data_ptr<float>(), cA.data_ptr<float>(), nullptr, res.data_ptr<float>(),
@@ -1925,6 +1976,8 @@ pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, c
     node->F = F; node->H1 = H1; node->H2 = H2; node->has_bias = cfg->has_bias; node->act1 = cfg->act1; node->act2 = cfg->act2;
     node->vc = mx_all.unsafeGetTensorImpl()->version_counter();
     node->version = node->vc.current_version();
+    node->hop_rows = cfg->hops_bptt && !euclid && !with_reset && T <= N && T <= 128;
+    if (node->hop_rows) node->descs = cfg->descs;
     node->set_next_edges(torch::autograd::collect_next_edges(packed));
     torch::autograd::create_gradient_edge(mx_all, node);
   }
@@ -2743,6 +2796,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("handle", [](StepCfg& c) { return reinterpret_cast<int64_t>(&c); })
       .def("update_descs", &StepCfg::update_descs)
       .def("set_cached_flags", [](StepCfg& c, int f) { c.cached_flags = f; })
+      .def("set_hops_bptt", [](StepCfg& c, bool on) { c.hops_bptt = on; })
       .def("set_col_cache", [](StepCfg& c, bool on) { c.col_cache = on; })
       .def("cached_launches", [](StepCfg& c, int B) {   // launches per cached step (0: no cached form)
         return gcm_dense_rows_cached_launches(c.descs.empty() ? nullptr : c.descs.data(), (int)c.descs.size(),

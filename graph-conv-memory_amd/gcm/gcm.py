@@ -167,6 +167,12 @@ class DenseGCM(torch.nn.Module):
         # (csrc/rows_cached_lean.hip: the step resolved on the host, the arguments its loads need preloaded into SGPRs,
         # layer 2's weights in flight under layer 1).  False (env GCM_LEAN_STEP=0): k_step_rows_cached_img4b (A/B)
         self.rows_lean_step = os.environ.get("GCM_LEAN_STEP", "1") == "1"
+        # True: the parameter backward of a chain of cached steps with forward temporal hops and host-known rows - the
+        # donated per-step loop from hidden = None while it stays below N steps, and rollout() from empty graphs at
+        # T <= N - runs in its GEMM form (csrc/rows_bptt_hops.hip: four small matrix products and one gather per graph,
+        # the records' live lists not read).  False (env GCM_BPTT_HOPS=0): k_bptt_cached_graph, which every other chain
+        # keeps (A/B); read when a chain is armed / a rollout starts
+        self.rows_hops_bptt = os.environ.get("GCM_BPTT_HOPS", "1") == "1"
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
         self.rollout_time_parallel = True
@@ -669,6 +675,7 @@ class DenseGCM(torch.nn.Module):
                     | (0 if self.rows_bookkeeping_wave else _hip.STEP_ONE_WAVE)
                     | (0 if self.rows_lean_step else _hip.STEP_NOT_LEAN))
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
+                cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
         mx, n2, a2, c2, donate = fast.run(x, nodes, adj, weights, num_nodes, root, flags, cfg.cpp_handle(),
                                           self.donate_state, need_dx, bool(fresh and self.rows_cached_steps))
         if donate:
@@ -907,6 +914,7 @@ class DenseGCM(torch.nn.Module):
                     and not (torch.is_grad_enabled() and obs.requires_grad)):
                 if cfg.cpp_handle():
                     flags = self._flag_word(obs.device)
+                    cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
                     if reset is None:
                         r = _ops._ext.module().rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True),
                                                                obs, flags)

@@ -897,6 +897,9 @@ int gcm_dense_rows_bptt_cached(const float* const* saved_host, const float* cons
                                const float* cache_agg1, const float* g_params_prev, float* g_params,
                                void* workspace, size_t workspace_bytes, int B, int N, int F, int H1, int H2,
                                gcm_stream_t stream);
+/* ... and its GEMM form for chains of forward temporal hops with host-known rows (cfg2; csrc/rows_bptt_hops.hip).
+ * Declared in gcm_hip_bptt_hops.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_bptt_hops.h"
 
 /* Parameter gradient of a rollout from the history gcm_dense_rollout_fwd /
  * gcm_dense_rollout_persistent_fwd kept, when neither the observations nor the initial node matrix
