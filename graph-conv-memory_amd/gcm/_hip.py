@@ -36,6 +36,8 @@ RESET_PROTOTYPES = _abi.prototypes(_RESET_HEADER)
 GIN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gin.h"))
 # and the section from gcm_hip_bptt_hops.h (the GEMM-form backward of forward-hop cached chains)
 BPTT_HOPS_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_bptt_hops.h"))
+# and the section from gcm_hip_resgated.h (ResGatedGraphConv / DenseResGatedGraphConv)
+RESGATED_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_resgated.h"))
 globals().update({name[4:]: value for name, value in _CONSTANTS.items()})   # GCM_ACT_TANH -> ACT_TANH, ...
 GCM_EUNSUPPORTED = _CONSTANTS["GCM_EUNSUPPORTED"]
 DIR = {d: _CONSTANTS["GCM_DIR_" + d.upper()] for d in ("forward", "backward", "both")}
@@ -77,6 +79,7 @@ def lib():
         bind(handle, RESET_PROTOTYPES)
         bind(handle, GIN_PROTOTYPES)
         bind(handle, BPTT_HOPS_PROTOTYPES)
+        bind(handle, RESGATED_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

@@ -1045,6 +1045,109 @@ def csr_transformerconv(x, w_all, b_all, w_beta, graph, heads, concat, root):
 
 
 # ---------------------------------------------------------------------------
+# DenseResGatedGraphConv / ResGatedGraphConv (PyG; csrc/resgatedconv.hip)
+# ---------------------------------------------------------------------------
+def _resgated_dims(w_all, root):
+    """C from the stacked weight [(4 if root else 3) C, Fi] = [W_key; W_query; W_value; W_skip]."""
+    C, rest = divmod(w_all.shape[0], 4 if root else 3)
+    assert rest == 0, "w_all must stack [W_key; W_query; W_value; W_skip]"
+    return C
+
+
+class _DenseResGatedConv(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (values are weights, 0 is no edge; gets a gradient when it asks for one), w_all [P,Fi] /
+    b_all [P] the stacked key, query, value (and skip) projections, bias [C] or None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, w_all, b_all, bias, root, add_loop):
+        x, adj, w_all, b_all = x.contiguous(), adj.contiguous(), w_all.contiguous(), b_all.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, adj, w_all, b_all, bias)
+        B, N, Fi = x.shape
+        C = _resgated_dims(w_all, root)
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert w_all.shape[1] == Fi and b_all.numel() == w_all.shape[0]
+        assert bias is None or bias.numel() == C
+        dims = (B, N, Fi, C, int(root))
+        out = torch.empty(B, N, C, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_dense_resgatedconv_fwd_workspace_bytes(*dims)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_resgatedconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all), _hip.ptr(b_all),
+              _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, adj, w_all, saved)
+        ctx.dims, ctx.add_loop, ctx.has_bias = dims, int(add_loop), bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, w_all, saved = ctx.saved_tensors
+        need_x, need_adj, need_w, need_b, need_bias = ctx.needs_input_grad[:5]
+        g_out = g_out.contiguous()
+        C = ctx.dims[3]
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_w = torch.empty_like(w_all) if need_w else None
+        g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
+        g_bias = torch.empty(C, device=x.device, dtype=_f32) if need_bias and ctx.has_bias else None
+        ws_bytes = _hip.lib().gcm_dense_resgatedconv_bwd_workspace_bytes(*ctx.dims)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_resgatedconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all),
+              _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_bias), _hip.ptr(g_adj),
+              _hip.ptr(ws), ws_bytes, *ctx.dims, ctx.add_loop, _hip.stream())
+        return g_x, g_adj, g_w, g_b, g_bias, None, None
+
+
+def dense_resgatedconv(x, adj, w_all, b_all, bias, root, add_loop):
+    """-> out [B,N,C]."""
+    return _DenseResGatedConv.apply(x, adj, w_all, b_all, bias, root, add_loop)
+
+
+class _CsrResGatedConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_all, b_all, bias, graph, root):
+        x, w_all, b_all = x.contiguous(), w_all.contiguous(), b_all.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, w_all, b_all, bias)
+        M, Fi = x.shape
+        C = _resgated_dims(w_all, root)
+        assert M == graph.M and w_all.shape[1] == Fi and b_all.numel() == w_all.shape[0]
+        assert bias is None or bias.numel() == C
+        dims = (M, graph.E, Fi, C, int(root))
+        out = torch.empty(M, C, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_csr_resgatedconv_fwd_workspace_bytes(*dims)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_resgatedconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(w_all),
+              _hip.ptr(b_all), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, _hip.stream())
+        ctx.save_for_backward(x, w_all, saved)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, dims, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_all, saved = ctx.saved_tensors
+        graph = ctx.graph
+        need_x, need_w, need_b, need_bias = ctx.needs_input_grad[:4]
+        g_out = g_out.contiguous()
+        col_ptr = rows = None
+        if graph.E > 0:
+            col_ptr, rows, _ = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(w_all) if need_w else None
+        g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
+        g_bias = torch.empty(ctx.dims[3], device=x.device, dtype=_f32) if need_bias and ctx.has_bias else None
+        ws_bytes = _hip.lib().gcm_csr_resgatedconv_bwd_workspace_bytes(*ctx.dims)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_resgatedconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(w_all), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w),
+              _hip.ptr(g_b), _hip.ptr(g_bias), _hip.ptr(ws), ws_bytes, *ctx.dims, _hip.stream())
+        return g_x, g_w, g_b, g_bias, None, None
+
+
+def csr_resgatedconv(x, w_all, b_all, bias, graph, root):
+    return _CsrResGatedConv.apply(x, w_all, b_all, bias, graph, root)
+
+
+# ---------------------------------------------------------------------------
 # mean / max aggregation: GraphConv(aggr=...), SAGEConv and their dense forms (csrc/aggrconv.hip)
 # ---------------------------------------------------------------------------
 AGGR = {"mean": _hip.AGGR_MEAN, "max": _hip.AGGR_MAX}

@@ -602,6 +602,109 @@ class TransformerConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
 
 
+def _resgated_params(conv, name, in_channels, out_channels, act, root_weight, bias):
+    if not isinstance(in_channels, int):
+        raise NotImplementedError(f"{name} with a tuple in_channels (bipartite graphs) is not implemented")
+    if act is not None and not isinstance(act, torch.nn.Sigmoid):
+        raise NotImplementedError(f"{name}(act=...) is not implemented for gates other than torch.nn.Sigmoid(); "
+                                  f"got {act!r}")
+    conv.in_channels, conv.out_channels, conv.root_weight = in_channels, out_channels, root_weight
+    conv.act = torch.nn.Sigmoid() if act is None else act
+    conv.lin_key = torch.nn.Linear(in_channels, out_channels)
+    conv.lin_query = torch.nn.Linear(in_channels, out_channels)
+    conv.lin_value = torch.nn.Linear(in_channels, out_channels)
+    conv.lin_skip = torch.nn.Linear(in_channels, out_channels, bias=False) if root_weight else None
+    conv.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+    conv.reset_parameters()
+
+
+def _resgated_reset(conv):
+    for lin in (conv.lin_key, conv.lin_query, conv.lin_value, conv.lin_skip):
+        if lin is not None:
+            lin.reset_parameters()
+    if conv.bias is not None:
+        torch.nn.init.zeros_(conv.bias)
+
+
+def _resgated_operands(conv):
+    """(w_all [P,F], b_all [P]): the projections stacked [key; query; value; skip] (the skip's bias slots zero), so
+    the kernels make one pass over x and autograd hands each Linear its slice of the stacked gradient."""
+    lins = [conv.lin_key, conv.lin_query, conv.lin_value]
+    w = [lin.weight for lin in lins]
+    b = [lin.bias for lin in lins]
+    if conv.root_weight:
+        w.append(conv.lin_skip.weight)
+        b.append(conv.lin_skip.weight.new_zeros(conv.out_channels))
+    return torch.cat(w), torch.cat(b)
+
+
+class DenseResGatedGraphConv(torch.nn.Module):
+    """The dense form of PyG's ResGatedGraphConv (Bresson & Laurent): k, q, v = lin_key(x), lin_query(x),
+    lin_value(x); out_i = lin_skip(x_i) + sum_j adj_ij sigmoid(k_i + q_j) * v_j + bias, * mask.  adj [B,N,N] float
+    (adj[b,i,j]: the edge j -> i): its values are weights and get a gradient when they ask for one, an entry equal
+    to 0 is no edge and is skipped; add_loop (default False, so that dense and sparse agree on one edge set)
+    overwrites the diagonal with 1.  The gate is per edge and per channel and is not normalised over the
+    neighbourhood; a row with no neighbour outputs lin_skip(x_i) + bias.  x [B,N,F]; F, out_channels <= 128.  Same
+    parameters as ResGatedGraphConv: the state_dicts interchange.  Forward and backward are HIP kernels
+    (csrc/resgatedconv.hip) that visit the set entries only and store no gate.  Not a DenseGraphConv: DenseGCM runs
+    a stack of these through its layered path."""
+
+    def __init__(self, in_channels, out_channels, act=None, root_weight=True, bias=True):
+        super().__init__()
+        _resgated_params(self, "DenseResGatedGraphConv", in_channels, out_channels, act, root_weight, bias)
+
+    def reset_parameters(self):
+        _resgated_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=False):
+        x, adj = _dense_inputs(x, adj)
+        _hip.on_device(self.lin_key.weight)
+        w_all, b_all = _resgated_operands(self)
+        out = _ops.dense_resgatedconv(x, adj, w_all, b_all, self.bias, self.root_weight, add_loop)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
+class ResGatedGraphConv(torch.nn.Module):
+    """PyG's ResGatedGraphConv (flow source_to_target) without edge features: edge_index [2,E] = (source, sink), x
+    [M,F]; out_i = lin_skip(x_i) + sum over the edges j -> i of sigmoid(lin_key(x_i) + lin_query(x_j)) *
+    lin_value(x_j) + bias.  The edges are used as given: no loop is added or removed, duplicates count once each; a
+    node without an in-edge outputs lin_skip(x_i) + bias.  edge_attr is accepted and ignored, as PyG does without
+    edge_dim.  Uses the `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed here.
+    Forward and backward are HIP kernels (csrc/resgatedconv.hip).  Not implemented (NotImplementedError): edge_dim,
+    a tuple in_channels, a gate `act` other than torch.nn.Sigmoid().  Not a GraphConv: SparseGCM runs a stack of
+    these through its generic path."""
+
+    def __init__(self, in_channels, out_channels, act=None, edge_dim=None, root_weight=True, bias=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("ResGatedGraphConv(edge_dim=...) is not implemented: edge features do not "
+                                      "enter the gate")
+        self.edge_dim = edge_dim
+        _resgated_params(self, "ResGatedGraphConv", in_channels, out_channels, act, root_weight, bias)
+
+    def reset_parameters(self):
+        _resgated_reset(self)
+
+    def forward(self, x, edge_index, edge_attr=None):
+        _hip.on_device(self.lin_key.weight)     # a CPU call fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("ResGatedGraphConv does not take a masked GraphIndex (k-hop subgraphs reach it "
+                             "relabelled)")
+        w_all, b_all = _resgated_operands(self)
+        return _ops.csr_resgatedconv(x, w_all, b_all, self.bias, graph, self.root_weight)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
