@@ -1148,6 +1148,126 @@ def csr_resgatedconv(x, w_all, b_all, bias, graph, root):
 
 
 # ---------------------------------------------------------------------------
+# DenseGatedGraphConv / GatedGraphConv (PyG; csrc/gatedgraphconv.hip)
+# ---------------------------------------------------------------------------
+def _gated_operands(weight, w_ih, w_hh, b_ih, b_hh):
+    """The contiguous parameters and (L, C) from weight [L,C,C], w_ih / w_hh [3C,C], b_ih / b_hh [3C] or None."""
+    weight, w_ih, w_hh = weight.contiguous(), w_ih.contiguous(), w_hh.contiguous()
+    b_ih = None if b_ih is None else b_ih.contiguous()
+    b_hh = None if b_hh is None else b_hh.contiguous()
+    L, C = weight.shape[0], weight.shape[1]
+    assert weight.shape == (L, C, C) and w_ih.shape == (3 * C, C) and w_hh.shape == (3 * C, C)
+    assert (b_ih is None or b_ih.numel() == 3 * C) and (b_hh is None or b_hh.numel() == 3 * C)
+    return weight, w_ih, w_hh, b_ih, b_hh, L, C
+
+
+def _gated_grads(ctx, weight, w_ih, first):
+    """Empty gradients of (weight, w_ih, w_hh, b_ih, b_hh) where asked for; `first`: the index of weight among the
+    inputs."""
+    need = ctx.needs_input_grad[first:first + 5]
+    C = weight.shape[1]
+    g_weight = torch.empty_like(weight) if need[0] else None
+    g_w_ih = torch.empty_like(w_ih) if need[1] else None
+    g_w_hh = torch.empty_like(w_ih) if need[2] else None
+    g_b_ih = torch.empty(3 * C, device=weight.device, dtype=_f32) if need[3] and ctx.has_bias[0] else None
+    g_b_hh = torch.empty(3 * C, device=weight.device, dtype=_f32) if need[4] and ctx.has_bias[1] else None
+    return g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh
+
+
+class _DenseGatedGraphConv(torch.autograd.Function):
+    """x [B,N,Fi] (Fi <= C), adj [B,N,N] (values are weights, 0 is no edge; gets a gradient when it asks for one),
+    weight [L,C,C], the GRU cell's w_ih / w_hh [3C,C] and b_ih / b_hh [3C] or None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, weight, w_ih, w_hh, b_ih, b_hh, add_loop):
+        x, adj = x.contiguous(), adj.contiguous()
+        weight, w_ih, w_hh, b_ih, b_hh, L, C = _gated_operands(weight, w_ih, w_hh, b_ih, b_hh)
+        _hip.on_device(x, adj, weight, w_ih, w_hh, b_ih, b_hh)
+        B, N, Fi = x.shape
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        out = torch.empty(B, N, C, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_dense_gatedgraphconv_fwd_workspace_bytes(B, N, C, L)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_gatedgraphconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(w_ih),
+              _hip.ptr(w_hh), _hip.ptr(b_ih), _hip.ptr(b_hh), _hip.ptr(out), _hip.ptr(saved), saved_bytes, B, N, Fi,
+              C, L, int(add_loop), _hip.stream())
+        ctx.save_for_backward(adj, weight, w_ih, w_hh, saved)
+        ctx.dims, ctx.add_loop, ctx.has_bias = (B, N, Fi, C, L), int(add_loop), (b_ih is not None, b_hh is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        adj, weight, w_ih, w_hh, saved = ctx.saved_tensors
+        B, N, Fi, C, L = ctx.dims
+        need_x, need_adj = ctx.needs_input_grad[:2]
+        g_out = g_out.contiguous()
+        g_x = torch.empty(B, N, Fi, device=adj.device, dtype=_f32) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh = _gated_grads(ctx, weight, w_ih, 2)
+        ws_bytes = _hip.lib().gcm_dense_gatedgraphconv_bwd_workspace_bytes(B, N, C, L)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=adj.device)
+        _call("gcm_dense_gatedgraphconv_bwd", _hip.ptr(g_out), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(w_ih),
+              _hip.ptr(w_hh), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_weight), _hip.ptr(g_w_ih), _hip.ptr(g_w_hh),
+              _hip.ptr(g_b_ih), _hip.ptr(g_b_hh), _hip.ptr(g_adj), _hip.ptr(ws), ws_bytes, B, N, Fi, C, L,
+              ctx.add_loop, _hip.stream())
+        return g_x, g_adj, g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh, None
+
+
+def dense_gatedgraphconv(x, adj, weight, w_ih, w_hh, b_ih, b_hh, add_loop):
+    """-> out [B,N,C]."""
+    return _DenseGatedGraphConv.apply(x, adj, weight, w_ih, w_hh, b_ih, b_hh, add_loop)
+
+
+class _CsrGatedGraphConv(torch.autograd.Function):
+    """x [M,Fi] (Fi <= C); w_edge [E] in CSR order or None."""
+
+    @staticmethod
+    def forward(ctx, x, w_edge, weight, w_ih, w_hh, b_ih, b_hh, graph):
+        x = x.contiguous()
+        w_edge = None if w_edge is None else w_edge.contiguous()
+        weight, w_ih, w_hh, b_ih, b_hh, L, C = _gated_operands(weight, w_ih, w_hh, b_ih, b_hh)
+        _hip.on_device(x, w_edge, weight, w_ih, w_hh, b_ih, b_hh)
+        M, Fi = x.shape
+        assert M == graph.M and (w_edge is None or w_edge.numel() == graph.E)
+        out = torch.empty(M, C, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_csr_gatedgraphconv_fwd_workspace_bytes(M, graph.E, C, L)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_csr_gatedgraphconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(w_edge), _hip.ptr(weight), _hip.ptr(w_ih), _hip.ptr(w_hh), _hip.ptr(b_ih), _hip.ptr(b_hh),
+              _hip.ptr(out), _hip.ptr(saved), saved_bytes, M, graph.E, Fi, C, L, _hip.stream())
+        ctx.save_for_backward(w_edge, weight, w_ih, w_hh, saved)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (M, graph.E, Fi, C, L), (b_ih is not None, b_hh is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        w_edge, weight, w_ih, w_hh, saved = ctx.saved_tensors
+        graph = ctx.graph
+        M, E, Fi, C, L = ctx.dims
+        need_x, need_we = ctx.needs_input_grad[:2]
+        need_we = need_we and w_edge is not None
+        g_out = g_out.contiguous()
+        col_ptr = rows = perm = None
+        if E > 0:
+            col_ptr, rows, perm = graph.csc()
+        g_x = torch.empty(M, Fi, device=g_out.device, dtype=_f32) if need_x else None
+        g_we = torch.zeros_like(w_edge) if need_we else None
+        g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh = _gated_grads(ctx, weight, w_ih, 2)
+        ws_bytes = _hip.lib().gcm_csr_gatedgraphconv_bwd_workspace_bytes(M, E, C, L)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g_out.device)
+        _call("gcm_csr_gatedgraphconv_bwd", _hip.ptr(g_out), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_edge), _hip.ptr(weight), _hip.ptr(w_ih),
+              _hip.ptr(w_hh), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_weight), _hip.ptr(g_w_ih), _hip.ptr(g_w_hh),
+              _hip.ptr(g_b_ih), _hip.ptr(g_b_hh), _hip.ptr(g_we), _hip.ptr(ws), ws_bytes, M, E, Fi, C, L,
+              _hip.stream())
+        return g_x, g_we, g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh, None
+
+
+def csr_gatedgraphconv(x, w_edge, weight, w_ih, w_hh, b_ih, b_hh, graph):
+    return _CsrGatedGraphConv.apply(x, w_edge, weight, w_ih, w_hh, b_ih, b_hh, graph)
+
+
+# ---------------------------------------------------------------------------
 # mean / max aggregation: GraphConv(aggr=...), SAGEConv and their dense forms (csrc/aggrconv.hip)
 # ---------------------------------------------------------------------------
 AGGR = {"mean": _hip.AGGR_MEAN, "max": _hip.AGGR_MAX}

@@ -705,6 +705,104 @@ class ResGatedGraphConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
 
 
+def _gated_params(conv, out_channels, num_layers, bias):
+    if num_layers < 1:
+        raise ValueError(f"num_layers must be at least 1; got {num_layers}")
+    conv.out_channels, conv.num_layers = out_channels, num_layers
+    conv.weight = torch.nn.Parameter(torch.empty(num_layers, out_channels, out_channels))
+    conv.rnn = torch.nn.GRUCell(out_channels, out_channels, bias=bias)
+    conv.reset_parameters()
+
+
+def _gated_reset(conv):
+    bound = 1.0 / conv.out_channels ** 0.5      # PyG's uniform(out_channels, weight)
+    torch.nn.init.uniform_(conv.weight, -bound, bound)
+    conv.rnn.reset_parameters()
+
+
+def _gated_width(conv, x):
+    if x.shape[-1] > conv.out_channels:
+        raise ValueError("The number of input channels is not allowed to be larger than the number of output "
+                         "channels")
+
+
+def _gated_cell(conv):
+    """(w_ih, w_hh, b_ih, b_hh) of the GRU cell, whose own forward is never called."""
+    rnn = conv.rnn
+    return rnn.weight_ih, rnn.weight_hh, getattr(rnn, "bias_ih", None), getattr(rnn, "bias_hh", None)
+
+
+class DenseGatedGraphConv(torch.nn.Module):
+    """The dense form of PyG's GatedGraphConv (Li et al., Gated Graph Sequence Neural Networks): h_0 = x zero-padded
+    to out_channels columns; num_layers rounds of m = adj @ (h weight[l]), h = GRUCell(m, h); out = h, * mask.  adj
+    [B,N,N] float (adj[b,i,j]: the edge j -> i): its values are weights and get a gradient when they ask for one
+    (for every entry, also where adj is 0), an entry equal to 0 is no edge and is skipped; add_loop (default False,
+    so that dense and sparse agree on one edge set) overwrites the diagonal with 1.  A row with no neighbour still
+    updates through the cell with m = 0.  x [B,N,F] with F <= out_channels <= 128.  Same parameters as
+    GatedGraphConv (`weight` [num_layers,C,C], `rnn`: a torch.nn.GRUCell): the state_dicts interchange.  Forward
+    and backward are HIP kernels (csrc/gatedgraphconv.hip): one launch per round, the gates never leave the
+    registers.  Not a DenseGraphConv: DenseGCM runs a stack of these through its layered path."""
+
+    def __init__(self, out_channels, num_layers, bias=True):
+        super().__init__()
+        _gated_params(self, out_channels, num_layers, bias)
+
+    def reset_parameters(self):
+        _gated_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=False):
+        x, adj = _dense_inputs(x, adj)
+        _gated_width(self, x)
+        _hip.on_device(self.weight)
+        out = _ops.dense_gatedgraphconv(x, adj, self.weight, *_gated_cell(self), add_loop)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"
+
+
+class GatedGraphConv(torch.nn.Module):
+    """PyG's GatedGraphConv (flow source_to_target), aggr="add": edge_index [2,E] = (source, sink), x [M,F] with F <=
+    out_channels <= 128, zero-padded to out_channels; num_layers rounds of m_i = sum over the edges j -> i of w_ji
+    (h weight[l])_j, h = GRUCell(m, h).  The edges are used as given: no loop is added or removed, duplicates are
+    separate terms; a node without an in-edge still updates through the cell with m = 0.  edge_weight follows
+    GraphConv's rules (a wrong-length vector is ignored, SparseGCM's unit weights are not loaded) and gets a gradient
+    when it asks for one.  Uses the `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed
+    here.  Forward and backward are HIP kernels (csrc/gatedgraphconv.hip).  Other aggregations raise
+    NotImplementedError.  Not a GraphConv: SparseGCM runs a stack of these through its generic path."""
+
+    def __init__(self, out_channels, num_layers, aggr="add", bias=True):
+        super().__init__()
+        if aggr != "add":
+            raise NotImplementedError(f"GatedGraphConv(aggr='{aggr}') is not implemented: aggr must be 'add'")
+        self.aggr = aggr
+        _gated_params(self, out_channels, num_layers, bias)
+
+    def reset_parameters(self):
+        _gated_reset(self)
+
+    def forward(self, x, edge_index, edge_weight=None):
+        _gated_width(self, x)
+        _hip.on_device(x, self.weight)     # a CPU call fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("GatedGraphConv does not take a masked GraphIndex (k-hop subgraphs reach it "
+                             "relabelled)")
+        w = edge_weight
+        if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
+            w = None        # as GraphConv: a wrong-length vector is ignored, unit weights are not loaded
+        if w is not None and graph.csr_perm is not None:
+            w = w[graph.csr_perm]
+        return _ops.csr_gatedgraphconv(x, w, self.weight, *_gated_cell(self), graph)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
