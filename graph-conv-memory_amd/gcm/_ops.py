@@ -1268,6 +1268,119 @@ def csr_gatedgraphconv(x, w_edge, weight, w_ih, w_hh, b_ih, b_hh, graph):
 
 
 # ---------------------------------------------------------------------------
+# DenseTAGConv / TAGConv (PyG; csrc/tagconv.hip)
+# ---------------------------------------------------------------------------
+class _DenseTagConv(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (adj[b,i,j]: the weight of j -> i; gets a gradient when it asks for one), weight
+    [K+1,Fo,Fi] (the hop matrices stacked), bias [Fo] or None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, weight, bias, normalize, add_loop):
+        x, adj, weight = x.contiguous(), adj.contiguous(), weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        _hip.on_device(x, adj, weight, bias)
+        B, N, Fi = x.shape
+        K, Fo = weight.shape[0] - 1, weight.shape[1]
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert weight.shape == (K + 1, Fo, Fi) and (bias is None or bias.numel() == Fo)
+        out = torch.empty(B, N, Fo, device=x.device, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_dense_tagconv_fwd_workspace_bytes(B, N, Fi, K)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_tagconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out),
+              _hip.ptr(saved), saved_bytes, B, N, Fi, Fo, K, int(normalize), int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, adj, weight, saved)
+        ctx.dims, ctx.flags, ctx.has_bias = (B, N, Fi, Fo, K), (int(normalize), int(add_loop)), bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, weight, saved = ctx.saved_tensors
+        B, N, Fi, Fo, K = ctx.dims
+        need_x, need_adj, need_w, need_b = ctx.needs_input_grad[:4]
+        need_b = need_b and ctx.has_bias
+        g_out = g_out.contiguous()
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_w = torch.empty_like(weight) if need_w else None
+        g_b = torch.empty(Fo, device=x.device, dtype=_f32) if need_b else None
+        ws_bytes = _hip.lib().gcm_dense_tagconv_bwd_workspace_bytes(B, N, Fi, Fo, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _call("gcm_dense_tagconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(saved),
+              _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, K,
+              ctx.flags[0], ctx.flags[1], _hip.stream())
+        return g_x, g_adj, g_w, g_b, None, None
+
+
+def dense_tagconv(x, adj, weight, bias, normalize, add_loop):
+    """-> out [B,N,Fo]."""
+    return _DenseTagConv.apply(x, adj, weight, bias, normalize, add_loop)
+
+
+class _CsrTagConv(torch.autograd.Function):
+    """x [M,Fi]; w_edge [E] in CSR order or None (unit weights); weight [K+1,Fo,Fi]."""
+
+    @staticmethod
+    def forward(ctx, x, w_edge, weight, bias, graph, normalize):
+        x, weight = x.contiguous(), weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        w_edge = None if w_edge is None else w_edge.contiguous()
+        _hip.on_device(x, w_edge, weight, bias)
+        M, Fi = x.shape
+        K, Fo = weight.shape[0] - 1, weight.shape[1]
+        E = graph.E
+        assert M == graph.M and (w_edge is None or w_edge.numel() == E)
+        assert weight.shape == (K + 1, Fo, Fi) and (bias is None or bias.numel() == Fo)
+        dev = x.device
+        dst = graph.dst_csr()
+        coef = torch.empty(E, device=dev, dtype=_f32)
+        dinv = torch.empty(M, device=dev, dtype=_f32)
+        loops = torch.empty(2, M, device=dev, dtype=_f32)      # gcn_norm's loop terms: none are added here
+        loop_e = torch.empty(M, device=dev, dtype=_i64)
+        _call("gcm_gcn_norm", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(w_edge),
+              _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loops[0]), _hip.ptr(loops[1]), _hip.ptr(loop_e), M, E,
+              int(normalize), 0, 0.0, _hip.stream())
+        out = torch.empty(M, Fo, device=dev, dtype=_f32)
+        saved_bytes = _hip.lib().gcm_csr_tagconv_fwd_workspace_bytes(M, Fi, K)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_csr_tagconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(coef),
+              _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, M, E, Fi, Fo, K,
+              _hip.stream())
+        ctx.save_for_backward(x, weight, dst, coef, dinv, saved)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (M, E, Fi, Fo, K), bias is not None
+        ctx.normalize, ctx.has_w = int(normalize), w_edge is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, weight, dst, coef, dinv, saved = ctx.saved_tensors
+        graph = ctx.graph
+        M, E, Fi, Fo, K = ctx.dims
+        need_x, need_we, need_w, need_b = ctx.needs_input_grad[:4]
+        need_b = need_b and ctx.has_bias
+        need_we = need_we and ctx.has_w
+        g_out = g_out.contiguous()
+        dev = x.device
+        col_ptr = rows = perm = None
+        if (need_x or need_we) and E > 0:
+            col_ptr, rows, perm = graph.csc()
+        g_x = torch.empty_like(x) if need_x else None
+        g_we = torch.zeros(E, device=dev, dtype=_f32) if need_we else None
+        g_w = torch.empty_like(weight) if need_w else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws_bytes = _hip.lib().gcm_csr_tagconv_bwd_workspace_bytes(M, E, Fi, Fo, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _call("gcm_csr_tagconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(coef), _hip.ptr(dinv),
+              _hip.ptr(weight), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_we), _hip.ptr(g_w), _hip.ptr(g_b),
+              _hip.ptr(ws), ws_bytes, M, E, Fi, Fo, K, ctx.normalize, _hip.stream())
+        return g_x, g_we, g_w, g_b, None, None
+
+
+def csr_tagconv(x, w_edge, weight, bias, graph, normalize):
+    return _CsrTagConv.apply(x, w_edge, weight, bias, graph, normalize)
+
+
+# ---------------------------------------------------------------------------
 # mean / max aggregation: GraphConv(aggr=...), SAGEConv and their dense forms (csrc/aggrconv.hip)
 # ---------------------------------------------------------------------------
 AGGR = {"mean": _hip.AGGR_MEAN, "max": _hip.AGGR_MAX}

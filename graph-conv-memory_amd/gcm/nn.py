@@ -803,6 +803,102 @@ class GatedGraphConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"
 
 
+def _tag_params(conv, in_channels, out_channels, K, bias, normalize):
+    if K < 0:
+        raise ValueError(f"K must be at least 0; got {K}")
+    conv.in_channels, conv.out_channels, conv.K, conv.normalize = in_channels, out_channels, K, normalize
+    conv.lins = torch.nn.ModuleList(torch.nn.Linear(in_channels, out_channels, bias=False) for _ in range(K + 1))
+    if bias:
+        conv.bias = torch.nn.Parameter(torch.zeros(out_channels))
+    else:
+        conv.register_parameter("bias", None)
+
+
+def _tag_reset(conv):
+    for lin in conv.lins:
+        lin.reset_parameters()
+    if conv.bias is not None:
+        torch.nn.init.zeros_(conv.bias)
+
+
+def _tag_weight(conv):
+    """The hop matrices stacked [K+1, out, in]: the kernels' operand (the stack's backward hands each its slice)."""
+    return torch.stack([lin.weight for lin in conv.lins])
+
+
+class DenseTAGConv(torch.nn.Module):
+    """The dense form of PyG's TAGConv (Du et al., Topology Adaptive Graph Convolutional Networks), a K-hop polynomial
+    filter in one layer: h_0 = x, h_k = A^ h_{k-1}, out = (sum_{k=0..K} h_k lins[k].weight^T + bias) * mask.  adj
+    [B,N,N] float32 (adj[b,i,j]: the weight of the edge j -> i; 2-D and a batch of one are broadcast) gets a gradient
+    when it asks for one, for every entry, also where adj is 0, the degree term of its row included; add_loop (default
+    False, so that dense and sparse agree on one edge set) overwrites the diagonal with 1 before the degrees are
+    taken, and that diagonal gets gradient 0.  With normalize (the default) A^ = D^-1/2 A D^-1/2, deg_i = sum_j A_ij,
+    d_i = deg_i^-1/2 and 0 where deg_i == 0 (no clamp to 1 as in DenseGCNConv: dense and sparse agree); otherwise A^
+    = adj.  Faithful to PyG on directed graphs: with normalize a node WITHOUT in-edges has d = 0 and sends nothing -
+    in a TemporalBackedge memory that is the oldest node; add_loop=True or normalize=False avoids it.  K = 0 is the
+    plain linear layer.  x [B,N,F]; in_channels, out_channels <= 128; float32.  Same parameters as TAGConv
+    (lins.k.weight, bias): the state_dicts interchange.  Forward and backward are HIP kernels (csrc/tagconv.hip): for
+    N <= 128 every hop runs in one launch with the adjacency read once.  Not a DenseGraphConv: DenseGCM runs a stack
+    of these through its layered path."""
+
+    def __init__(self, in_channels, out_channels, K=3, bias=True, normalize=True):
+        super().__init__()
+        _tag_params(self, in_channels, out_channels, K, bias, normalize)
+
+    def reset_parameters(self):
+        _tag_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=False):
+        x, adj = _dense_inputs(x, adj)
+        _hip.on_device(self.lins[0].weight)
+        out = _ops.dense_tagconv(x, adj, _tag_weight(self), self.bias, self.normalize, add_loop)
+        if mask is not None:
+            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, K={self.K})"
+
+
+class TAGConv(torch.nn.Module):
+    """PyG's TAGConv (flow source_to_target), a K-hop polynomial filter in one layer: edge_index [2,E] = (source,
+    sink), x [M,F]; h_0 = x, h_k[i] = sum over the edges j -> i of c_e h_{k-1}[j], out = sum_{k=0..K} h_k
+    lins[k].weight^T + bias.  With normalize (the default) c_e is PyG's gcn_norm(add_self_loops=False): deg_i = the
+    sum of the weights INTO i, d_i = deg_i^-1/2 and 0 where deg_i == 0, c_e = d_src w_e d_dst; otherwise c_e = w_e.
+    The edges are used as given: no loop is added or removed (i -> i is an ordinary edge), duplicates are separate
+    terms.  Faithful to PyG on directed graphs: with normalize a node WITHOUT in-edges has d = 0 and sends nothing -
+    in a TemporalBackedge memory that is the oldest node; normalize=False avoids it.  edge_weight follows
+    GatedGraphConv's rules (a wrong-length vector is ignored, SparseGCM's unit weights are not loaded) and gets a
+    gradient when it asks for one.  K = 0 is the plain linear layer.  in_channels, out_channels <= 128; float32.
+    Parameters as PyG's (lins.k.weight, bias).  Uses the `edge_index.gcm_graph` index SparseGCM attaches; any other
+    edge list is indexed here.  Forward and backward are HIP kernels (csrc/tagconv.hip), one launch per hop.  Not a
+    GraphConv: SparseGCM runs a stack of these through its generic path."""
+
+    def __init__(self, in_channels, out_channels, K=3, bias=True, normalize=True):
+        super().__init__()
+        _tag_params(self, in_channels, out_channels, K, bias, normalize)
+
+    def reset_parameters(self):
+        _tag_reset(self)
+
+    def forward(self, x, edge_index, edge_weight=None):
+        _hip.on_device(x, self.lins[0].weight)     # a CPU call fails here, before the index is built
+        graph = getattr(edge_index, "gcm_graph", None)
+        if graph is None or graph.M != x.shape[0]:
+            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+        if graph.mask is not None:
+            raise ValueError("TAGConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        w = edge_weight
+        if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
+            w = None        # as GraphConv: a wrong-length vector is ignored, unit weights are not loaded
+        if w is not None and graph.csr_perm is not None:
+            w = w[graph.csr_perm]
+        return _ops.csr_tagconv(x, w, _tag_weight(self), self.bias, graph, self.normalize)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, K={self.K})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
