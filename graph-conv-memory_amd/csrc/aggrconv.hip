@@ -102,16 +102,6 @@ int linear_fwd(const float* agg, const float* x, const float* w_rel, const float
   return launch_lin2(p, s);
 }
 
-// C[R, Fi] = G[R, Fo] W[Fo, Fi]
-int times_w(const float* g, const float* w, float* c, int64_t R, int Fi, int Fo, hipStream_t s) {
-  MmArgs p = mm_args();
-  p.A = g, p.a_is = Fo, p.a_ks = 1;
-  p.B = w, p.b_ks = Fi, p.b_js = 1;
-  p.C = c, p.c_is = Fi, p.c_js = 1;
-  p.M = (int)R, p.N = Fi, p.K = Fo;
-  return launch_mm(p, 1, s);
-}
-
 // the parameter gradients every leg shares: g_bias = colsum(G), g_w_rel = G^T agg, g_w_root = G^T x
 int param_grads(const float* g_out, const float* agg, const float* x, float* g_w_rel, float* g_w_root,
                 float* g_bias, float* slabs, int64_t R, int Fi, int Fo, hipStream_t s) {
@@ -392,9 +382,10 @@ struct DenseWs {
 DenseWs dense_ws(int B, int N, int Fi, int Fo) {
   DenseWs w;
   const int64_t rows = (int64_t)B * N;
-  w.t = 0;
-  w.c = align256(rows * std::max(Fi, Fo) * sizeof(float));
-  w.slabs = w.c + align256(rows * sizeof(float));
+  Carve cv;
+  w.t = cv.take(rows * std::max(Fi, Fo) * sizeof(float));
+  w.c = cv.take(rows * sizeof(float));
+  w.slabs = cv.at;  // the last field: not rounded up
   w.total = w.slabs + slab_floats(rows, Fi, Fo) * sizeof(float);
   return w;
 }
@@ -441,7 +432,7 @@ extern "C" int gcm_dense_aggrconv_bwd(const float* g_out, const float* x, const 
       if ((rc = launch_lin2(q, s))) return rc;
     }
     if (g_adj) {  // g_adj_ij = dinv_i <dAgg_i, x_j> + c_i
-      if ((rc = times_w(g_out, w_rel, t, rows, Fi, Fo, s))) return rc;
+      if ((rc = mm_gw(g_out, w_rel, t, rows, Fi, Fo, s))) return rc;
       hipLaunchKernelGGL(k_aggr_dense_rowterm, dim3(blocks(rows, 4)), dim3(256), 0, s, t, agg, deg, dinv, c, rows,
                          Fi);
       if ((rc = gcm_launch_status())) return rc;
@@ -456,8 +447,8 @@ extern "C" int gcm_dense_aggrconv_bwd(const float* g_out, const float* x, const 
     return GCM_OK;
   }
   if (!g_x) return GCM_OK;
-  if ((rc = times_w(g_out, w_rel, t, rows, Fi, Fo, s))) return rc;                    // dAgg
-  if (w_root && (rc = times_w(g_out, w_root, g_x, rows, Fi, Fo, s))) return rc;       // the root term
+  if ((rc = mm_gw(g_out, w_rel, t, rows, Fi, Fo, s))) return rc;                    // dAgg
+  if (w_root && (rc = mm_gw(g_out, w_root, g_x, rows, Fi, Fo, s))) return rc;       // the root term
   const dim3 grid(blocks(N, XR), B);
   const int accumulate = w_root != nullptr;
   switch ((Fi + 31) / 32) {
@@ -497,8 +488,9 @@ struct CsrWs {
 };
 CsrWs csr_ws(int64_t M, int Fi, int Fo) {
   CsrWs w;
-  w.dagg = 0;
-  w.slabs = align256(M * Fi * sizeof(float));
+  Carve cv;
+  w.dagg = cv.take(M * Fi * sizeof(float));
+  w.slabs = cv.at;  // the last field: not rounded up
   w.total = w.slabs + slab_floats(M, Fi, Fo) * sizeof(float);
   return w;
 }
@@ -532,9 +524,9 @@ extern "C" int gcm_csr_aggrconv_bwd(const float* g_out, const float* x, const fl
   if ((rc = param_grads(g_out, agg, x, g_w_rel, g_w_root, g_bias, slabs, M, Fi, Fo, s))) return rc;
   const bool has_e = E > 0;
   if (!g_x && !(g_edge && has_e)) return GCM_OK;
-  if ((rc = times_w(g_out, w_rel, dagg, M, Fi, Fo, s))) return rc;
+  if ((rc = mm_gw(g_out, w_rel, dagg, M, Fi, Fo, s))) return rc;
   if (g_x) {
-    if (w_root && (rc = times_w(g_out, w_root, g_x, M, Fi, Fo, s))) return rc;
+    if (w_root && (rc = mm_gw(g_out, w_root, g_x, M, Fi, Fo, s))) return rc;
     const dim3 grid(blocks(M * Fi, 256));
     const int accumulate = w_root != nullptr;
     if (aggr == GCM_AGGR_MAX)

@@ -1,5 +1,6 @@
-// The bit image of a dense attention pattern, shared by the attention layers (csrc/gatconv.hip,
-// csrc/transformerconv.hip): the adjacency is read once, the kernels read the image.
+// The bit image of a dense neighbourhood pattern, shared by the attention and gated layers (csrc/gatconv.hip,
+// csrc/transformerconv.hip, csrc/resgatedconv.hip, csrc/gatedgraphconv.hip): the adjacency is read once, the kernels
+// read the image.  Also their lane-group reduction.
 #pragma once
 #include "gcn_mm.h"
 
@@ -22,6 +23,31 @@ __global__ __launch_bounds__(256) void k_gat_mask_bits(const float* __restrict__
     const int w = j0 / 32 + lane;
     if (lane < 2 && w < W) bits[(size_t)row * W + w] = lane ? (unsigned)(m >> 32) : (unsigned)m;
   }
+}
+
+// bitsT[b, j, w] bit t = bits[b, 32 w + t, j / 32] bit j % 32.  One thread per word.
+__global__ __launch_bounds__(256) void k_mask_bits_t(const unsigned* __restrict__ bits, unsigned* __restrict__ bitsT,
+                                                     int64_t R, int N, int W) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= R * W) return;
+  const int64_t row = t / W;
+  const int w = (int)(t - row * W);
+  const int j = (int)(row % N);
+  const size_t rb = (size_t)(row - j);
+  unsigned word = 0;
+  for (int k = 0; k < 32; ++k) {
+    const int i = w * 32 + k;
+    if (i < N) word |= ((bits[(rb + i) * W + (j >> 5)] >> (j & 31)) & 1u) << k;
+  }
+  bitsT[t] = word;
+}
+
+// the sum over a group of G adjacent lanes
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;  // the same bits in every lane of the group
 }
 
 }  // namespace

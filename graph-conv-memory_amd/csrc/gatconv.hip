@@ -454,20 +454,10 @@ __global__ void k_gat_csr_gy(const int64_t* __restrict__ col_ptr, const int64_t*
   if (cc == h * C) gss[j * H + h] = g;
 }
 
-// y = x W^T over R rows
-int linear(const float* x, const float* w, float* y, int64_t R, int Fi, int HC, hipStream_t s) {
-  MmArgs p = mm_args();
-  p.A = x, p.a_is = Fi, p.a_ks = 1;
-  p.B = w, p.b_ks = 1, p.b_js = Fi;
-  p.C = y, p.c_is = HC, p.c_js = 1;
-  p.M = (int)R, p.N = HC, p.K = Fi;
-  return launch_mm(p, 1, s);
-}
-
 // the forward's common tail and head: y, scores; out from o
 int fwd_head(const float* x, const float* w, const float* att_src, const float* att_dst, float* y, float* s_src,
              float* s_dst, int64_t R, int Fi, int H, int C, hipStream_t s) {
-  int rc = linear(x, w, y, R, Fi, H * C, s);
+  int rc = mm_xwt(x, w, nullptr, y, R, Fi, H * C, s);
   if (rc) return rc;
   hipLaunchKernelGGL(k_gat_scores, dim3(blocks(R * H, 256)), dim3(256), 0, s, y, att_src, att_dst, s_src, s_dst,
                      R, H, C);
@@ -496,19 +486,14 @@ BwdWs bwd_ws(int64_t R, int64_t nparts_rows, bool sparse, int64_t E, int Fi, int
   wgrad_split(R, &nsplit, &kchunk);
   const size_t slab_f = std::max<size_t>((size_t)nsplit * HC * Fi,
                                          (size_t)colsum_slabs(R) * std::max<int64_t>(HC, Fo));
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  w.dO = take(R * HC * 4), w.gy = take(R * HC * 4), w.tsrc = take(R * HC * 4), w.tdst = take(R * HC * 4);
-  w.delta = take(R * H * 4), w.gss = take(R * H * 4), w.part = take(nparts_rows * H * 4);
+  Carve c;
+  w.dO = c.take(R * HC * 4), w.gy = c.take(R * HC * 4), w.tsrc = c.take(R * HC * 4), w.tdst = c.take(R * HC * 4);
+  w.delta = c.take(R * H * 4), w.gss = c.take(R * H * 4), w.part = c.take(nparts_rows * H * 4);
   const int64_t loop_rows = sparse ? R : 0;
-  w.alpha = take(E * H * 4), w.de = take(E * H * 4), w.ploop = take(loop_rows * H * 4);
-  w.deloop = take(loop_rows * H * 4);
-  w.slabs = take(slab_f * 4);
-  w.total = o;
+  w.alpha = c.take(E * H * 4), w.de = c.take(E * H * 4), w.ploop = c.take(loop_rows * H * 4);
+  w.deloop = c.take(loop_rows * H * 4);
+  w.slabs = c.take(slab_f * 4);
+  w.total = c.at;
   return w;
 }
 
@@ -527,14 +512,7 @@ int bwd_tail(const float* x, const float* w, const float* y, const float* att_ds
   if (rc) return rc;
   if (g_att_src && (rc = colsum(tsrc, R, HC, g_att_src, slabs, s))) return rc;
   if (g_att_dst && (rc = colsum(tdst, R, HC, g_att_dst, slabs, s))) return rc;
-  if (g_x) {  // g_x = gy W
-    MmArgs p = mm_args();
-    p.A = gy, p.a_is = HC, p.a_ks = 1;
-    p.B = w, p.b_ks = Fi, p.b_js = 1;
-    p.C = g_x, p.c_is = Fi, p.c_js = 1;
-    p.M = (int)R, p.N = Fi, p.K = HC;
-    if ((rc = launch_mm(p, 1, s))) return rc;
-  }
+  if (g_x && (rc = mm_gw(gy, w, g_x, R, Fi, HC, s))) return rc;  // g_x = gy W
   if (g_w && (rc = wgrad(gy, x, g_w, slabs, R, Fi, HC, s))) return rc;
   return GCM_OK;
 }

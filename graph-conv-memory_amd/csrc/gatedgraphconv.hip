@@ -85,23 +85,6 @@ __device__ __forceinline__ void gg_nbr_sum(const Nbr& g, int64_t r, const float*
   }
 }
 
-// bitsT[b, j, w] bit t = bits[b, 32 w + t, j / 32] bit j % 32.  One thread per word.
-__global__ __launch_bounds__(256) void k_gg_bits_t(const unsigned* __restrict__ bits, unsigned* __restrict__ bitsT,
-                                                   int64_t R, int N, int W) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= R * W) return;
-  const int64_t row = t / W;
-  const int w = (int)(t - row * W);
-  const int j = (int)(row % N);
-  const size_t rb = (size_t)(row - j);
-  unsigned word = 0;
-  for (int k = 0; k < 32; ++k) {
-    const int i = w * 32 + k;
-    if (i < N) word |= ((bits[(rb + i) * W + (j >> 5)] >> (j & 31)) & 1u) << k;
-  }
-  bitsT[t] = word;
-}
-
 // h0[r, c] = c < Fi ? x[r, c] : 0
 __global__ __launch_bounds__(256) void k_gg_pad(const float* __restrict__ x, float* __restrict__ h0, int64_t R, int Fi,
                                                 int C) {
@@ -451,8 +434,7 @@ __global__ __launch_bounds__(256) void k_gg_edge_grad(const int64_t* __restrict_
     const float* s = pj + (size_t)col[e] * C;
     float d = 0.f;
     for (int c = gl; c < C; c += 32) d = fmaf(gm[(size_t)i * C + c], s[c], d);
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) d += __shfl_xor(d, off);
+    d = group_sum<32>(d);
     if (gl == 0) g_ew[e] = accumulate ? g_ew[e] + d : d;
   }
 }
@@ -477,15 +459,6 @@ size_t gg_saved_bytes(int64_t R, int C, int L, int64_t bit_words) {
   return ((size_t)SLOTS * L * R * C + (size_t)bit_words) * 4;
 }
 
-// split-K plan of a parameter gradient summed over K rows: chunks of 64 rows (one fp32 chain over a few hundred rows
-// loses the tests' bound), of more once that would be over 512 slabs
-void gg_split(int64_t K, int* nsplit, int* kchunk) {
-  int64_t c = std::max<int64_t>(64, (K + 511) / 512);
-  c = (c + KT - 1) / KT * KT;
-  *kchunk = (int)c;
-  *nsplit = (int)((K + c - 1) / c);
-}
-
 constexpr int WL_BATCH = 64;  // rounds per launch of the g_weight product (grid.z = rounds x splits <= 65535)
 
 struct BwdWs {
@@ -493,23 +466,18 @@ struct BwdWs {
 };
 BwdWs gg_bwd_ws(int64_t R, int C, int L, int64_t bit_words) {
   BwdWs w;
-  const size_t RC = align256((size_t)R * C * 4);
+  const size_t RC = (size_t)R * C * 4;
   int nsK, nsR, kc;
-  gg_split((int64_t)L * R, &nsK, &kc);
-  gg_split(R, &nsR, &kc);
+  wgrad_split64((int64_t)L * R, &nsK, &kc);
+  wgrad_split64(R, &nsR, &kc);
   size_t slab_f = (size_t)nsK * 3 * C * C;
   slab_f = std::max(slab_f, (size_t)std::min(L, WL_BATCH) * nsR * C * C);
   slab_f = std::max(slab_f, (size_t)colsum_slabs((int64_t)L * R) * 4 * C);
-  w.G = 0;
-  w.gP = w.G + align256((size_t)L * R * 4 * C * 4);
-  w.gM = w.gP + align256((size_t)L * R * C * 4);
-  w.gHa = w.gM + RC;
-  w.gHb = w.gHa + RC;
-  w.P = w.gHb + RC;
-  w.sums = w.P + RC;
-  w.bitsT = w.sums + align256((size_t)4 * C * 4);
-  w.slabs = w.bitsT + align256((size_t)bit_words * 4);
-  w.total = w.slabs + align256(slab_f * 4);
+  Carve c;
+  w.G = c.take((size_t)L * R * 4 * C * 4), w.gP = c.take((size_t)L * R * C * 4);
+  w.gM = c.take(RC), w.gHa = c.take(RC), w.gHb = c.take(RC), w.P = c.take(RC);
+  w.sums = c.take((size_t)4 * C * 4), w.bitsT = c.take((size_t)bit_words * 4), w.slabs = c.take(slab_f * 4);
+  w.total = c.at;
   return w;
 }
 
@@ -623,7 +591,7 @@ int gg_backward(const Nbr& gt, const int64_t* row_ptr, const int64_t* col, const
   const float* h_all = sv + gg_slot(SLOT_H, 0, L, R, C);
   const float* m_all = sv + gg_slot(SLOT_M, 0, L, R, C);
   int ns, kc;
-  gg_split(LR, &ns, &kc);
+  wgrad_split64(LR, &ns, &kc);
   // g_w[rows, :] = sum over all L R rows of G[:, col0 + rows]^T y
   auto wgrad = [&](int col0, int rows, const float* y, float* g) -> int {
     MmArgs q = mm_args();
@@ -640,7 +608,7 @@ int gg_backward(const Nbr& gt, const int64_t* row_ptr, const int64_t* col, const
     if ((rc = wgrad(3 * C, C, h_all, o.g_w_hh + (size_t)2 * C * C))) return rc;
   }
   if (o.g_weight) {  // g_weight[l] = h_l^T g_p_l, the rounds batched
-    gg_split(R, &ns, &kc);
+    wgrad_split64(R, &ns, &kc);
     for (int l0 = 0; l0 < L; l0 += WL_BATCH) {
       const int nb = std::min(WL_BATCH, L - l0);
       MmArgs q = mm_args();
@@ -716,7 +684,7 @@ extern "C" int gcm_dense_gatedgraphconv_bwd(const float* g_out, const float* adj
   const float* sv = (const float*)saved;
   const unsigned* bits = (const unsigned*)(sv + (size_t)SLOTS * L * R * C);
   unsigned* bitsT = (unsigned*)((char*)workspace + K.bitsT);
-  hipLaunchKernelGGL(k_gg_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
+  hipLaunchKernelGGL(k_mask_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
   const int rc = gcm_launch_status();
   if (rc) return rc;
   Nbr gt = {};

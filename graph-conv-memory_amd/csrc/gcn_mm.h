@@ -132,6 +132,27 @@ int launch_mm(MmArgs p, int nsplit, hipStream_t s) {
   return gcm_launch_status();
 }
 
+// y[R, Fo] = x[R, Fi] W^T (+ bias),  W [Fo, Fi]
+int mm_xwt(const float* x, const float* w, const float* bias, float* y, int64_t R, int Fi, int Fo, hipStream_t s) {
+  MmArgs p = mm_args();
+  p.A = x, p.a_is = Fi, p.a_ks = 1;
+  p.B = w, p.b_ks = 1, p.b_js = Fi;
+  p.C = y, p.c_is = Fo, p.c_js = 1, p.c_bias = bias;
+  p.M = (int)R, p.N = Fo, p.K = Fi;
+  return launch_mm(p, 1, s);
+}
+
+// c[R, Fi] = g[R, Fo] W,  W [Fo, Fi];  batch > 1: c + b * c_bs = g (W + b * w_bs), the one g against a stack of W
+int mm_gw(const float* g, const float* w, float* c, int64_t R, int Fi, int Fo, hipStream_t s, int batch = 1,
+          int64_t w_bs = 0, int64_t c_bs = 0) {
+  MmArgs p = mm_args();
+  p.A = g, p.a_is = Fo, p.a_ks = 1;
+  p.B = w, p.b_bs = w_bs, p.b_ks = Fi, p.b_js = 1;
+  p.C = c, p.c_bs = c_bs, p.c_is = Fi, p.c_js = 1;
+  p.M = (int)R, p.N = Fi, p.K = Fo, p.batch = batch;
+  return launch_mm(p, 1, s);
+}
+
 // split-K plan of a weight gradient summed over R rows: (splits, rows per split)
 void wgrad_split(int64_t R, int* nsplit, int* kchunk) {
   int n = (int)std::min<int64_t>(256, (R + 511) / 512);
@@ -142,11 +163,23 @@ void wgrad_split(int64_t R, int* nsplit, int* kchunk) {
   *nsplit = (int)((R + c - 1) / c);
 }
 
-// g[Fo, Fi] = sum_r gy[r, :]^T x[r, :]   (rows r < R), via split-K slabs and gcm_sum_slabs
-int wgrad(const float* gy, const float* x, float* g, float* slabs, int64_t R, int Fi, int Fo,
-          hipStream_t s) {
+// The plan of the layers whose gradients pass through a gate (ResGated, GatedGraph): chunks of 64 rows (of more once
+// that would be over 512 slabs).  wgrad_split keeps a few hundred rows in one fp32 accumulation chain, whose rounding
+// error grows with the chain's length: at 300 rows it is six times that of chains of 64.
+void wgrad_split64(int64_t R, int* nsplit, int* kchunk) {
+  int64_t c = std::max<int64_t>(64, (R + 511) / 512);
+  c = (c + KT - 1) / KT * KT;
+  *kchunk = (int)c;
+  *nsplit = (int)((R + c - 1) / c);
+}
+
+using SplitPlan = void (*)(int64_t R, int* nsplit, int* kchunk);
+
+// g[Fo, Fi] = sum_r gy[r, :]^T x[r, :]   (rows r < R), via split-K slabs of the given plan and gcm_sum_slabs
+int wgrad(const float* gy, const float* x, float* g, float* slabs, int64_t R, int Fi, int Fo, hipStream_t s,
+          SplitPlan plan = wgrad_split) {
   int nsplit, kchunk;
-  wgrad_split(R, &nsplit, &kchunk);
+  plan(R, &nsplit, &kchunk);
   MmArgs p = mm_args();
   p.A = gy, p.a_is = 1, p.a_ks = Fo;
   p.B = x, p.b_ks = Fi, p.b_js = 1;
@@ -183,5 +216,15 @@ int64_t colsum_slabs(int64_t R) { return (R + COLSUM_ROWS - 1) / COLSUM_ROWS; }
 unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// offsets of the fields of a workspace, each rounded up to 256 bytes: `at` is the total once every field is taken
+struct Carve {
+  size_t at = 0;
+  size_t take(size_t bytes) {
+    const size_t o = at;
+    at += align256(bytes);
+    return o;
+  }
+};
 
 }  // namespace

@@ -250,13 +250,8 @@ extern "C" int gcm_dense_gcnconv_fwd(const float* x, const float* adj, const flo
                      add_loop, loop_value);
   int rc = gcm_launch_status();
   if (rc) return rc;
-  MmArgs p = mm_args();  // y = x W^T over all B*N rows
-  p.A = x, p.a_is = Fi, p.a_ks = 1;
-  p.B = w, p.b_ks = 1, p.b_js = Fi;
-  p.C = y, p.c_is = Fo, p.c_js = 1;
-  p.M = (int)rows, p.N = Fo, p.K = Fi;
-  if ((rc = launch_mm(p, 1, s))) return rc;
-  p = mm_args();  // out = d_i sum_k A_ik d_k y_k + bias;  agg = sum_k A_ik d_k y_k
+  if ((rc = mm_xwt(x, w, nullptr, y, rows, Fi, Fo, s))) return rc;  // y = x W^T over all B*N rows
+  MmArgs p = mm_args();  // out = d_i sum_k A_ik d_k y_k + bias;  agg = sum_k A_ik d_k y_k
   p.A = adj, p.a_bs = (int64_t)N * N, p.a_is = N, p.a_ks = 1;
   p.a_diag = add_loop, p.diag_val = loop_value;
   p.B = y, p.b_bs = (int64_t)N * Fo, p.b_ks = Fo, p.b_js = 1, p.b_kscale = dinv;
@@ -318,14 +313,7 @@ extern "C" int gcm_dense_gcnconv_bwd(const float* g_out, const float* x, const f
   hipLaunchKernelGGL(k_gcn_dense_rowgrad, dim3(blocks(rows, 4)), dim3(256), 0, s, g_out, agg, y, deg, dinv,
                      gz, c, rows, Fo);
   if ((rc = gcm_launch_status())) return rc;
-  if (g_x) {  // g_x = gY W
-    p = mm_args();
-    p.A = gz, p.a_is = Fo, p.a_ks = 1;
-    p.B = w, p.b_ks = Fi, p.b_js = 1;
-    p.C = g_x, p.c_is = Fi, p.c_js = 1;
-    p.M = (int)rows, p.N = Fi, p.K = Fo;
-    if ((rc = launch_mm(p, 1, s))) return rc;
-  }
+  if (g_x && (rc = mm_gw(gz, w, g_x, rows, Fi, Fo, s))) return rc;  // g_x = gY W
   if (g_w && (rc = wgrad(gz, x, g_w, slabs, rows, Fi, Fo, s))) return rc;
   if (g_adj) {  // g_adj_ij = d_i d_j <G_i, y_j> + c_i, 0 on an overwritten diagonal
     p = mm_args();
@@ -426,12 +414,7 @@ extern "C" int gcm_csr_gcnconv_bwd(const float* g_out, const float* x, const flo
   if (g_bias && (rc = colsum(g_out, M, Fo, g_bias, slabs, s))) return rc;
   if (g_w && (rc = wgrad(g_out, agg, g_w, slabs, M, Fi, Fo, s))) return rc;
   if (!g_x && !g_edge) return GCM_OK;
-  MmArgs p = mm_args();  // dAgg = G W
-  p.A = g_out, p.a_is = Fo, p.a_ks = 1;
-  p.B = w, p.b_ks = Fi, p.b_js = 1;
-  p.C = dagg, p.c_is = Fi, p.c_js = 1;
-  p.M = (int)M, p.N = Fi, p.K = Fo;
-  if ((rc = launch_mm(p, 1, s))) return rc;
+  if ((rc = mm_gw(g_out, w, dagg, M, Fi, Fo, s))) return rc;  // dAgg = G W
   const bool has_e = E > 0;
   if (g_x) {
     hipLaunchKernelGGL(k_gcn_scatter_T, dim3(blocks(M * Fi, 256)), dim3(256), 0, s, dagg,

@@ -20,7 +20,7 @@
 //   k_rg_dense_fwd  by row block: out.
 //   k_rg_dense_drow by row block: g_k[i] = sum_j a g_i v_j s (1 - s), and g_adj[i,j] = sum_c g_i s v_j when asked for
 //                   (a group sum per entry; then every entry of the row is visited, set or not).
-//   k_rg_dense_dcol by neighbour block over the transposed image (k_rg_bits_t): the group owns neighbours, tiles of 32
+//   k_rg_dense_dcol by neighbour block over the transposed image (k_mask_bits_t): the group owns neighbours, tiles of 32
 //                   rows (k and g_out staged): g_q[j] = sum_i a g_i v_j s (1 - s), g_v[j] = sum_i a g_i s.
 // Neither backward sweep sums across workgroups.
 // sparse: a lane group per destination walks its CSR row (forward, and g_k in the backward); g_q and g_v are gathered
@@ -39,34 +39,10 @@ constexpr int RG_RPG = 4;  // rows (dense) of a lane group
 // finite for every argument: z -> -inf gives 1 / (1 + inf) = 0, z -> +inf gives 1 / (1 + 0) = 1, and s (1 - s) = 0
 __device__ __forceinline__ float rg_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
 
-template <int G>
-__device__ __forceinline__ float rg_group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;  // the same bits in every lane of the group
-}
-
 // the bits of word w that name a neighbour < N
 __device__ __forceinline__ unsigned rg_valid_word(int w, int N) {
   const int n = N - w * 32;
   return n >= 32 ? 0xffffffffu : (n <= 0 ? 0u : (1u << n) - 1u);
-}
-
-// bitsT[b, j, w] bit t = bits[b, 32 w + t, j / 32] bit j % 32.  One thread per word.
-__global__ __launch_bounds__(256) void k_rg_bits_t(const unsigned* __restrict__ bits, unsigned* __restrict__ bitsT,
-                                                   int64_t R, int N, int W) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= R * W) return;
-  const int64_t row = t / W;
-  const int w = (int)(t - row * W);
-  const int j = (int)(row % N);
-  const size_t rb = (size_t)(row - j);
-  unsigned word = 0;
-  for (int k = 0; k < 32; ++k) {
-    const int i = w * 32 + k;
-    if (i < N) word |= ((bits[(rb + i) * W + (j >> 5)] >> (j & 31)) & 1u) << k;
-  }
-  bitsT[t] = word;
 }
 
 // stage columns [c0, c0 + C) and [c1, c1 + C) of the 32 rows from `first` of src (row stride ld) as [row][CP]
@@ -218,7 +194,7 @@ __global__ __launch_bounds__(256) void k_rg_dense_drow(const unsigned* __restric
           gk[r][ch] = fmaf(a * t, s * (1.f - s), gk[r][ch]);
         }
         if (g_adj) {
-          ga = rg_group_sum<G>(ga);
+          ga = group_sum<G>(ga);
           if (gl == 0) g_adj[abase + jj] = loop ? 0.f : ga;
         }
       }
@@ -434,33 +410,11 @@ struct Saved {
 };
 Saved saved_layout(const Dims& d, int64_t bit_words) {
   Saved s;
-  s.proj = 0;
-  s.bits = align256((size_t)d.R * d.P * 4);
-  s.total = s.bits + align256((size_t)bit_words * 4);
+  Carve c;
+  s.proj = c.take((size_t)d.R * d.P * 4);
+  s.bits = c.take((size_t)bit_words * 4);
+  s.total = c.at;
   return s;
-}
-
-// The weight gradient g[P,Fi] = sum_r gp[r,:]^T x[r,:] as split-K slabs over chunks of 64 rows (of more once that
-// would be over 512 slabs), summed in order by gcm_sum_slabs.  gcn_mm.h's wgrad_split keeps a few hundred rows in one
-// fp32 accumulation chain, whose rounding error grows with the chain's length: at 300 rows it is six times that of
-// chains of 64.
-void rg_wgrad_split(int64_t R, int* nsplit, int* kchunk) {
-  int64_t c = std::max<int64_t>(64, (R + 511) / 512);
-  c = (c + KT - 1) / KT * KT;
-  *kchunk = (int)c;
-  *nsplit = (int)((R + c - 1) / c);
-}
-
-int rg_wgrad(const float* gy, const float* x, float* g, float* slabs, int64_t R, int Fi, int Fo, hipStream_t s) {
-  int nsplit, kchunk;
-  rg_wgrad_split(R, &nsplit, &kchunk);
-  MmArgs p = mm_args();
-  p.A = gy, p.a_is = 1, p.a_ks = Fo;
-  p.B = x, p.b_ks = Fi, p.b_js = 1;
-  p.C = slabs, p.c_is = Fi, p.c_js = 1, p.c_ss = (int64_t)Fo * Fi;
-  p.M = Fo, p.N = Fi, p.K = (int)R, p.kchunk = kchunk;
-  const int rc = launch_mm(p, nsplit, s);
-  return rc ? rc : gcm_sum_slabs(slabs, nsplit, Fo * Fi, g, s);
 }
 
 // backward workspace: gp = [dK|dQ|dV|dR] [R,P], the transposed image (dense), slabs for the weight gradient and the
@@ -471,24 +425,19 @@ struct BwdWs {
 BwdWs bwd_ws(const Dims& d, int64_t bit_words) {
   BwdWs w;
   int nsplit, kchunk;
-  rg_wgrad_split(d.R, &nsplit, &kchunk);
+  wgrad_split64(d.R, &nsplit, &kchunk);
   const size_t slab_f = std::max<size_t>((size_t)nsplit * d.P * d.Fi, (size_t)colsum_slabs(d.R) * d.P);
-  w.gp = 0;
-  w.bitsT = align256((size_t)d.R * d.P * 4);
-  w.slabs = w.bitsT + align256((size_t)bit_words * 4);
-  w.total = w.slabs + align256(slab_f * 4);
+  Carve c;
+  w.gp = c.take((size_t)d.R * d.P * 4);
+  w.bitsT = c.take((size_t)bit_words * 4);
+  w.slabs = c.take(slab_f * 4);
+  w.total = c.at;
   return w;
 }
 
 // [k|q|v|r] = x W_all^T + b_all
 int project(const float* x, const float* w_all, const float* b_all, float* proj, const Dims& d, hipStream_t s) {
-  MmArgs p = mm_args();
-  p.A = x, p.a_is = d.Fi, p.a_ks = 1;
-  p.B = w_all, p.b_ks = 1, p.b_js = d.Fi;
-  p.C = proj, p.c_is = d.P, p.c_js = 1;
-  p.c_bias = b_all;
-  p.M = (int)d.R, p.N = d.P, p.K = d.Fi;
-  return launch_mm(p, 1, s);
+  return mm_xwt(x, w_all, b_all, proj, d.R, d.Fi, d.P, s);
 }
 
 // from the stacked projection gradient: g_b_all = its column sums, g_x = gp W_all, g_w_all = gp^T x; g_bias = the
@@ -500,15 +449,8 @@ int bwd_tail(const float* g_out, const float* x, const float* w_all, float* g_x,
   int rc;
   if (g_bias && (rc = colsum(g_out, d.R, d.C, g_bias, slabs, s))) return rc;
   if (g_b_all && (rc = colsum(gp, d.R, d.P, g_b_all, slabs, s))) return rc;
-  if (g_x) {
-    MmArgs p = mm_args();
-    p.A = gp, p.a_is = d.P, p.a_ks = 1;
-    p.B = w_all, p.b_ks = d.Fi, p.b_js = 1;
-    p.C = g_x, p.c_is = d.Fi, p.c_js = 1;
-    p.M = (int)d.R, p.N = d.Fi, p.K = d.P;
-    if ((rc = launch_mm(p, 1, s))) return rc;
-  }
-  if (g_w_all && (rc = rg_wgrad(gp, x, g_w_all, slabs, d.R, d.Fi, d.P, s))) return rc;
+  if (g_x && (rc = mm_gw(gp, w_all, g_x, d.R, d.Fi, d.P, s))) return rc;
+  if (g_w_all && (rc = wgrad(gp, x, g_w_all, slabs, d.R, d.Fi, d.P, s, wgrad_split64))) return rc;
   return GCM_OK;
 }
 
@@ -589,7 +531,7 @@ extern "C" int gcm_dense_resgatedconv_bwd(const float* g_out, const float* x, co
   }
   if (g_x || g_w_all || g_b_all) {
     unsigned* bitsT = (unsigned*)(ws + K.bitsT);
-    hipLaunchKernelGGL(k_rg_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
+    hipLaunchKernelGGL(k_mask_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
     if ((rc = gcm_launch_status())) return rc;
     RG_LAUNCH(k_rg_dense_dcol, RG_DENSE_GRID, s, (const unsigned*)bitsT, adj, proj, d.P, g_out, gp, N, C, add_loop)
     if ((rc = gcm_launch_status())) return rc;

@@ -608,10 +608,11 @@ TagBwdWs tag_bwd_ws(int64_t R, int Fi, int Fo, int K) {
   const size_t slab_f =
       std::max<size_t>((size_t)nsplit * (K + 1) * Fo * Fi, (size_t)colsum_slabs(R) * Fo);
   const size_t hop = align256((size_t)R * Fi * sizeof(float));
-  w.t = 0;
-  w.u = w.t + align256((size_t)(K + 1) * R * Fi * sizeof(float));
-  w.c = w.u + std::max<size_t>(K, 1) * hop;
-  w.slabs = w.c + align256(R * sizeof(float));
+  Carve cv;
+  w.t = cv.take((size_t)(K + 1) * R * Fi * sizeof(float));
+  w.u = cv.take(std::max<size_t>(K, 1) * hop);
+  w.c = cv.take(R * sizeof(float));
+  w.slabs = cv.at;  // the last field: not rounded up
   w.total = w.slabs + slab_f * sizeof(float);
   return w;
 }
@@ -642,12 +643,7 @@ int tag_param_grads(const float* g, const float* x, const float* hs, float* g_we
 
 // T[k] = g W_k for k = 0..K in one batched launch (K == 0: straight into dest0)
 int tag_gw(const float* g, const float* w, float* T, int64_t R, int Fi, int Fo, int K, hipStream_t s) {
-  MmArgs p = mm_args();
-  p.A = g, p.a_is = Fo, p.a_ks = 1;
-  p.B = w, p.b_bs = (int64_t)Fo * Fi, p.b_ks = Fi, p.b_js = 1;
-  p.C = T, p.c_bs = R * Fi, p.c_is = Fi, p.c_js = 1;
-  p.M = (int)R, p.N = Fi, p.K = Fo, p.batch = K + 1;
-  return launch_mm(p, 1, s);
+  return mm_gw(g, w, T, R, Fi, Fo, s, K + 1, (int64_t)Fo * Fi, R * Fi);
 }
 
 bool tag_unsupported(int64_t R, int Fi, int Fo, int K) {

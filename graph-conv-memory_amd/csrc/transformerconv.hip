@@ -444,13 +444,6 @@ __global__ __launch_bounds__(256) void k_tr_dense_dkv(const unsigned* __restrict
 // ---------------------------------------------------------------------------
 // sparse.  A group of G lanes per (destination i, head h); lane gl holds channels gl and gl + G (C <= 2 G).
 // ---------------------------------------------------------------------------
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;  // the same bits in every lane of the group
-}
-
 // <a, row[h C ...]> over the group
 template <int G>
 __device__ __forceinline__ float group_dot(float a0, float a1, const float* __restrict__ row, int gl, int C) {
@@ -577,16 +570,11 @@ struct Saved {
 };
 Saved saved_layout(const Dims& d, int64_t bit_words) {
   Saved s;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t was = at;
-    at += align256(bytes);
-    return was;
-  };
-  s.proj = take((size_t)d.R * d.P * 4), s.o = take((size_t)d.R * d.HC * 4);
-  s.m = take((size_t)d.R * d.H * 4), s.l = take((size_t)d.R * d.H * 4);
-  s.gate = take((size_t)d.R * 4), s.bits = take((size_t)bit_words * 4);
-  s.total = at;
+  Carve c;
+  s.proj = c.take((size_t)d.R * d.P * 4), s.o = c.take((size_t)d.R * d.HC * 4);
+  s.m = c.take((size_t)d.R * d.H * 4), s.l = c.take((size_t)d.R * d.H * 4);
+  s.gate = c.take((size_t)d.R * 4), s.bits = c.take((size_t)bit_words * 4);
+  s.total = c.at;
   return s;
 }
 
@@ -601,29 +589,18 @@ BwdWs bwd_ws(const Dims& d, int64_t E) {
   wgrad_split(d.R, &nsplit, &kchunk);
   const size_t slab_f = std::max<size_t>((size_t)nsplit * d.P * d.Fi,
                                          (size_t)colsum_slabs(d.R) * std::max(d.P, 3 * d.D));
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t was = at;
-    at += align256(bytes);
-    return was;
-  };
-  w.dO = take((size_t)d.R * d.HC * 4), w.gp = take((size_t)d.R * d.P * 4), w.delta = take((size_t)d.R * d.H * 4);
-  w.t = take((size_t)d.R * 3 * d.D * 4);
-  w.alpha = take((size_t)E * d.H * 4), w.ds = take((size_t)E * d.H * 4);
-  w.slabs = take(slab_f * 4);
-  w.total = at;
+  Carve c;
+  w.dO = c.take((size_t)d.R * d.HC * 4), w.gp = c.take((size_t)d.R * d.P * 4);
+  w.delta = c.take((size_t)d.R * d.H * 4), w.t = c.take((size_t)d.R * 3 * d.D * 4);
+  w.alpha = c.take((size_t)E * d.H * 4), w.ds = c.take((size_t)E * d.H * 4);
+  w.slabs = c.take(slab_f * 4);
+  w.total = c.at;
   return w;
 }
 
 // [q|k|v|r] = x W_all^T + b_all
 int project(const float* x, const float* w_all, const float* b_all, float* proj, const Dims& d, hipStream_t s) {
-  MmArgs p = mm_args();
-  p.A = x, p.a_is = d.Fi, p.a_ks = 1;
-  p.B = w_all, p.b_ks = 1, p.b_js = d.Fi;
-  p.C = proj, p.c_is = d.P, p.c_js = 1;
-  p.c_bias = b_all;
-  p.M = (int)d.R, p.N = d.P, p.K = d.Fi;
-  return launch_mm(p, 1, s);
+  return mm_xwt(x, w_all, b_all, proj, d.R, d.Fi, d.P, s);
 }
 
 int fwd_tail(const float* w_beta, float* out, const Saved& L, char* sv, const Dims& d, int concat, hipStream_t s) {
@@ -651,14 +628,7 @@ int bwd_tail(const float* x, const float* w_all, float* g_x, float* g_w_all, flo
   float* slabs = (float*)(ws + K.slabs);
   int rc;
   if (g_b_all && (rc = colsum(gp, d.R, d.P, g_b_all, slabs, s))) return rc;
-  if (g_x) {
-    MmArgs p = mm_args();
-    p.A = gp, p.a_is = d.P, p.a_ks = 1;
-    p.B = w_all, p.b_ks = d.Fi, p.b_js = 1;
-    p.C = g_x, p.c_is = d.Fi, p.c_js = 1;
-    p.M = (int)d.R, p.N = d.Fi, p.K = d.P;
-    if ((rc = launch_mm(p, 1, s))) return rc;
-  }
+  if (g_x && (rc = mm_gw(gp, w_all, g_x, d.R, d.Fi, d.P, s))) return rc;
   if (g_w_all && (rc = wgrad(gp, x, g_w_all, slabs, d.R, d.Fi, d.P, s))) return rc;
   return GCM_OK;
 }

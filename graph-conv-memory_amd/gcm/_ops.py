@@ -559,6 +559,38 @@ def sparse_extract(feats, T, taus, node_off, B, t_pad, flags):
     return _SparseExtract.apply(feats, T, taus, node_off, B, t_pad, flags)
 
 
+def _scratch(name, *dims, device):
+    """(uint8 tensor, nbytes) of the size the library's `<name>_workspace_bytes(*dims)` asks for: a backward's
+    workspace or what a forward saves for its backward."""
+    nbytes = getattr(_hip.lib(), name + "_workspace_bytes")(*dims)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _csc_or_none(graph, wanted):
+    """graph.csc() = (col_ptr, rows, perm) when wanted, else three Nones: building the CSC view launches work."""
+    return graph.csc() if wanted else (None, None, None)
+
+
+def _contig(t):
+    return None if t is None else t.contiguous()
+
+
+def _gcn_norm(graph, w_edge, normalize, add_self_loops, fill):
+    """gcm_gcn_norm over the CSR entries (w_edge [E] in CSR order or None) -> (dst [E], coef [E], dinv [M], loop_w
+    [M], loop_coef [M], loop_e [M])."""
+    M, E, dev = graph.M, graph.E, graph.col.device
+    dst = graph.dst_csr()
+    coef = torch.empty(E, device=dev, dtype=_f32)
+    dinv = torch.empty(M, device=dev, dtype=_f32)
+    loop_w = torch.empty(M, device=dev, dtype=_f32)
+    loop_coef = torch.empty(M, device=dev, dtype=_f32)
+    loop_e = torch.empty(M, device=dev, dtype=_i64)
+    _call("gcm_gcn_norm", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(w_edge),
+          _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loop_w), _hip.ptr(loop_coef), _hip.ptr(loop_e), M, E,
+          int(normalize), int(add_self_loops), float(fill), _hip.stream())
+    return dst, coef, dinv, loop_w, loop_coef, loop_e
+
+
 class _CsrGraphConv(torch.autograd.Function):
     """x [M,Fi]; w_edge [E] in CSR order or None."""
 
@@ -566,8 +598,8 @@ class _CsrGraphConv(torch.autograd.Function):
     def forward(ctx, x, w_edge, w_rel, b_rel, w_root, graph, act):
         x = x.contiguous()
         w_rel, w_root = w_rel.contiguous(), w_root.contiguous()
-        b_rel = None if b_rel is None else b_rel.contiguous()
-        w_edge = None if w_edge is None else w_edge.contiguous()
+        b_rel = _contig(b_rel)
+        w_edge = _contig(w_edge)
         _hip.on_device(x, w_edge, w_rel, b_rel, w_root)
         M, Fi = x.shape
         Fo = w_rel.shape[0]
@@ -595,16 +627,13 @@ class _CsrGraphConv(torch.autograd.Function):
         dev = x.device
         lib = _hip.lib()
         E = graph.E
-        col_ptr = rows = perm = None
-        if (need_x or need_we) and E > 0:
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_we) and E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_we = torch.zeros_like(w_edge) if need_we else None
         g_wrel = torch.empty_like(w_rel) if need_wrel else None
         g_wroot = torch.empty_like(w_root) if need_wroot else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = lib.gcm_csr_graphconv_bwd_workspace_bytes(M, Fi, Fo)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_csr_graphconv_bwd", M, Fi, Fo, device=dev)
         _call("gcm_csr_graphconv_bwd", _hip.ptr(g_out), _hip.ptr(out), _hip.ptr(x), _hip.ptr(agg),
               _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(col_ptr), _hip.ptr(rows),
               _hip.ptr(perm), _hip.ptr(w_edge), _hip.ptr(graph.mask), _hip.ptr(w_rel),
@@ -624,7 +653,7 @@ class _DenseGCNConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, w, bias, add_loop, loop_value):
         x, adj, w = x.contiguous(), adj.contiguous(), w.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, adj, w, bias)
         B, N, Fi = x.shape
         Fo = w.shape[0]
@@ -658,8 +687,7 @@ class _DenseGCNConv(torch.autograd.Function):
         g_adj = torch.empty_like(adj) if need_adj else None
         g_w = torch.empty_like(w) if need_w else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = lib.gcm_dense_gcnconv_bwd_workspace_bytes(B, N, Fi, Fo)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_dense_gcnconv_bwd", B, N, Fi, Fo, device=dev)
         _call("gcm_dense_gcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w), _hip.ptr(y),
               _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_w),
               _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, ctx.loop[0], ctx.loop[1], _hip.stream())
@@ -676,23 +704,15 @@ class _CsrGCNConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_edge, w, bias, graph, normalize, add_self_loops, fill):
         x, w = x.contiguous(), w.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        w_edge = None if w_edge is None else w_edge.contiguous()
+        bias = _contig(bias)
+        w_edge = _contig(w_edge)
         _hip.on_device(x, w_edge, w, bias)
         M, Fi = x.shape
         Fo = w.shape[0]
         E = graph.E
         assert M == graph.M
         dev = x.device
-        dst = graph.dst_csr()
-        coef = torch.empty(E, device=dev, dtype=_f32)
-        dinv = torch.empty(M, device=dev, dtype=_f32)
-        loop_w = torch.empty(M, device=dev, dtype=_f32)
-        loop_coef = torch.empty(M, device=dev, dtype=_f32)
-        loop_e = torch.empty(M, device=dev, dtype=_i64)
-        _call("gcm_gcn_norm", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(w_edge),
-              _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loop_w), _hip.ptr(loop_coef), _hip.ptr(loop_e), M, E,
-              int(normalize), int(add_self_loops), float(fill), _hip.stream())
+        dst, coef, dinv, loop_w, loop_coef, loop_e = _gcn_norm(graph, w_edge, normalize, add_self_loops, fill)
         out = torch.empty(M, Fo, device=dev, dtype=_f32)
         agg = torch.empty(M, Fi, device=dev, dtype=_f32) if any(ctx.needs_input_grad) else None
         _call("gcm_csr_gcnconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(coef),
@@ -716,15 +736,12 @@ class _CsrGCNConv(torch.autograd.Function):
         g_out = g_out.contiguous()
         dev = x.device
         lib = _hip.lib()
-        col_ptr = rows = perm = None
-        if (need_x or need_we) and E > 0:
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_we) and E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_we = torch.zeros_like(w_edge) if need_we else None
         g_w = torch.empty_like(w) if need_w else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = lib.gcm_csr_gcnconv_bwd_workspace_bytes(M, E, Fi, Fo)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_csr_gcnconv_bwd", M, E, Fi, Fo, device=dev)
         _call("gcm_csr_gcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(agg), _hip.ptr(graph.row_ptr),
               _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm),
               _hip.ptr(w_edge), _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loop_w), _hip.ptr(loop_coef),
@@ -767,8 +784,7 @@ class _DenseGINAggregate(torch.autograd.Function):
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
         g_eps = torch.empty_like(eps) if need_eps else None
-        ws_bytes = _hip.lib().gcm_dense_gin_bwd_workspace_bytes(B, N, F)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_dense_gin_bwd", B, N, F, device=dev)
         _call("gcm_dense_gin_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(eps), _hip.ptr(g_x),
               _hip.ptr(g_adj), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, B, N, F, ctx.add_loop, _hip.stream())
         return g_x, g_adj, g_eps, None
@@ -804,13 +820,10 @@ class _CsrGINAggregate(torch.autograd.Function):
         need_x, need_eps, _ = ctx.needs_input_grad
         g_h = g_h.contiguous()
         dev = x.device
-        col_ptr = rows = None
-        if need_x and E > 0:
-            col_ptr, rows, _ = graph.csc()
+        col_ptr, rows, _ = _csc_or_none(graph, need_x and E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_eps = torch.empty_like(eps) if need_eps else None
-        ws_bytes = _hip.lib().gcm_csr_gin_bwd_workspace_bytes(M, E, F)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_csr_gin_bwd", M, E, F, device=dev)
         _call("gcm_csr_gin_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(eps), _hip.ptr(col_ptr), _hip.ptr(rows),
               _hip.ptr(g_x), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, M, E, F, _hip.stream())
         return g_x, g_eps, None
@@ -830,7 +843,7 @@ class _DenseGATConv(torch.autograd.Function):
     def forward(ctx, x, adj, w, att_src, att_dst, bias, heads, concat, add_loop, slope):
         x, adj, w = x.contiguous(), adj.contiguous(), w.contiguous()
         att_src, att_dst = att_src.contiguous().view(-1), att_dst.contiguous().view(-1)
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, adj, w, att_src, att_dst, bias)
         B, N, Fi = x.shape
         HC = w.shape[0]
@@ -864,8 +877,7 @@ class _DenseGATConv(torch.autograd.Function):
         g_as = torch.empty(H * C, device=x.device, dtype=_f32) if need_as else None
         g_ad = torch.empty(H * C, device=x.device, dtype=_f32) if need_ad else None
         g_b = torch.empty(H * C if concat else C, device=x.device, dtype=_f32) if need_b and has_bias else None
-        ws_bytes = lib.gcm_dense_gatconv_bwd_workspace_bytes(B, N, Fi, H, C, concat)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_dense_gatconv_bwd", B, N, Fi, H, C, concat, device=x.device)
         _call("gcm_dense_gatconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w), _hip.ptr(att_src),
               _hip.ptr(att_dst), _hip.ptr(y), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(stats[2]),
               _hip.ptr(stats[3]), _hip.ptr(bits), _hip.ptr(g_x), _hip.ptr(g_w),
@@ -885,7 +897,7 @@ class _CsrGATConv(torch.autograd.Function):
     def forward(ctx, x, w, att_src, att_dst, bias, graph, heads, concat, add_self_loops, slope):
         x, w = x.contiguous(), w.contiguous()
         att_src, att_dst = att_src.contiguous().view(-1), att_dst.contiguous().view(-1)
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, w, att_src, att_dst, bias)
         M, Fi = x.shape
         HC = w.shape[0]
@@ -915,16 +927,13 @@ class _CsrGATConv(torch.autograd.Function):
         need_x, need_w, need_as, need_ad, need_b = ctx.needs_input_grad[:5]
         g_out = g_out.contiguous()
         lib = _hip.lib()
-        col_ptr = rows = perm = None
-        if E > 0 and (need_x or need_w or need_as or need_ad):
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, E > 0 and (need_x or need_w or need_as or need_ad))
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w) if need_w else None
         g_as = torch.empty(H * C, device=x.device, dtype=_f32) if need_as else None
         g_ad = torch.empty(H * C, device=x.device, dtype=_f32) if need_ad else None
         g_b = torch.empty(H * C if concat else C, device=x.device, dtype=_f32) if need_b and has_bias else None
-        ws_bytes = lib.gcm_csr_gatconv_bwd_workspace_bytes(M, E, Fi, H, C, concat)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_csr_gatconv_bwd", M, E, Fi, H, C, concat, device=x.device)
         _call("gcm_csr_gatconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w), _hip.ptr(att_src),
               _hip.ptr(att_dst), _hip.ptr(y), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(stats[2]),
@@ -967,8 +976,7 @@ class _DenseTransformerConv(torch.autograd.Function):
         assert w_beta is None or w_beta.numel() == 3 * D
         dims = (B, N, Fi, H, C, int(concat), int(root))
         out = torch.empty(B, N, D, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_dense_transformerconv_fwd_workspace_bytes(*dims)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_dense_transformerconv_fwd", *dims, device=x.device)
         _call("gcm_dense_transformerconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all), _hip.ptr(b_all),
               _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, int(add_loop), _hip.stream())
         ctx.save_for_backward(x, w_all, w_beta, saved)
@@ -984,8 +992,7 @@ class _DenseTransformerConv(torch.autograd.Function):
         g_w = torch.empty_like(w_all) if need_w else None
         g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
         g_beta = torch.empty_like(w_beta) if need_beta and w_beta is not None else None
-        ws_bytes = _hip.lib().gcm_dense_transformerconv_bwd_workspace_bytes(*ctx.dims)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_dense_transformerconv_bwd", *ctx.dims, device=x.device)
         _call("gcm_dense_transformerconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w_all), _hip.ptr(w_beta),
               _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_beta), _hip.ptr(ws), ws_bytes,
               *ctx.dims, _hip.stream())
@@ -1009,8 +1016,7 @@ class _CsrTransformerConv(torch.autograd.Function):
         assert w_beta is None or w_beta.numel() == 3 * D
         dims = (M, graph.E, Fi, H, C, int(concat), int(root))
         out = torch.empty(M, D, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_csr_transformerconv_fwd_workspace_bytes(*dims)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_csr_transformerconv_fwd", *dims, device=x.device)
         _call("gcm_csr_transformerconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(w_all), _hip.ptr(b_all), _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims,
               _hip.stream())
@@ -1024,15 +1030,12 @@ class _CsrTransformerConv(torch.autograd.Function):
         graph = ctx.graph
         need_x, need_w, need_b, need_beta = ctx.needs_input_grad[:4]
         g_out = g_out.contiguous()
-        col_ptr = rows = perm = None
-        if graph.E > 0:
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, graph.E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w_all) if need_w else None
         g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
         g_beta = torch.empty_like(w_beta) if need_beta and w_beta is not None else None
-        ws_bytes = _hip.lib().gcm_csr_transformerconv_bwd_workspace_bytes(*ctx.dims)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_csr_transformerconv_bwd", *ctx.dims, device=x.device)
         _call("gcm_csr_transformerconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr),
               _hip.ptr(graph.col), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_all),
               _hip.ptr(w_beta), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_beta),
@@ -1061,7 +1064,7 @@ class _DenseResGatedConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, w_all, b_all, bias, root, add_loop):
         x, adj, w_all, b_all = x.contiguous(), adj.contiguous(), w_all.contiguous(), b_all.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, adj, w_all, b_all, bias)
         B, N, Fi = x.shape
         C = _resgated_dims(w_all, root)
@@ -1070,8 +1073,7 @@ class _DenseResGatedConv(torch.autograd.Function):
         assert bias is None or bias.numel() == C
         dims = (B, N, Fi, C, int(root))
         out = torch.empty(B, N, C, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_dense_resgatedconv_fwd_workspace_bytes(*dims)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_dense_resgatedconv_fwd", *dims, device=x.device)
         _call("gcm_dense_resgatedconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all), _hip.ptr(b_all),
               _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, int(add_loop), _hip.stream())
         ctx.save_for_backward(x, adj, w_all, saved)
@@ -1089,8 +1091,7 @@ class _DenseResGatedConv(torch.autograd.Function):
         g_w = torch.empty_like(w_all) if need_w else None
         g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
         g_bias = torch.empty(C, device=x.device, dtype=_f32) if need_bias and ctx.has_bias else None
-        ws_bytes = _hip.lib().gcm_dense_resgatedconv_bwd_workspace_bytes(*ctx.dims)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_dense_resgatedconv_bwd", *ctx.dims, device=x.device)
         _call("gcm_dense_resgatedconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_all),
               _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_bias), _hip.ptr(g_adj),
               _hip.ptr(ws), ws_bytes, *ctx.dims, ctx.add_loop, _hip.stream())
@@ -1106,7 +1107,7 @@ class _CsrResGatedConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_all, b_all, bias, graph, root):
         x, w_all, b_all = x.contiguous(), w_all.contiguous(), b_all.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, w_all, b_all, bias)
         M, Fi = x.shape
         C = _resgated_dims(w_all, root)
@@ -1114,8 +1115,7 @@ class _CsrResGatedConv(torch.autograd.Function):
         assert bias is None or bias.numel() == C
         dims = (M, graph.E, Fi, C, int(root))
         out = torch.empty(M, C, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_csr_resgatedconv_fwd_workspace_bytes(*dims)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_csr_resgatedconv_fwd", *dims, device=x.device)
         _call("gcm_csr_resgatedconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(w_all),
               _hip.ptr(b_all), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, _hip.stream())
         ctx.save_for_backward(x, w_all, saved)
@@ -1128,15 +1128,12 @@ class _CsrResGatedConv(torch.autograd.Function):
         graph = ctx.graph
         need_x, need_w, need_b, need_bias = ctx.needs_input_grad[:4]
         g_out = g_out.contiguous()
-        col_ptr = rows = None
-        if graph.E > 0:
-            col_ptr, rows, _ = graph.csc()
+        col_ptr, rows, _ = _csc_or_none(graph, graph.E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w_all) if need_w else None
         g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
         g_bias = torch.empty(ctx.dims[3], device=x.device, dtype=_f32) if need_bias and ctx.has_bias else None
-        ws_bytes = _hip.lib().gcm_csr_resgatedconv_bwd_workspace_bytes(*ctx.dims)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_csr_resgatedconv_bwd", *ctx.dims, device=x.device)
         _call("gcm_csr_resgatedconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(w_all), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w),
               _hip.ptr(g_b), _hip.ptr(g_bias), _hip.ptr(ws), ws_bytes, *ctx.dims, _hip.stream())
@@ -1153,8 +1150,8 @@ def csr_resgatedconv(x, w_all, b_all, bias, graph, root):
 def _gated_operands(weight, w_ih, w_hh, b_ih, b_hh):
     """The contiguous parameters and (L, C) from weight [L,C,C], w_ih / w_hh [3C,C], b_ih / b_hh [3C] or None."""
     weight, w_ih, w_hh = weight.contiguous(), w_ih.contiguous(), w_hh.contiguous()
-    b_ih = None if b_ih is None else b_ih.contiguous()
-    b_hh = None if b_hh is None else b_hh.contiguous()
+    b_ih = _contig(b_ih)
+    b_hh = _contig(b_hh)
     L, C = weight.shape[0], weight.shape[1]
     assert weight.shape == (L, C, C) and w_ih.shape == (3 * C, C) and w_hh.shape == (3 * C, C)
     assert (b_ih is None or b_ih.numel() == 3 * C) and (b_hh is None or b_hh.numel() == 3 * C)
@@ -1186,8 +1183,7 @@ class _DenseGatedGraphConv(torch.autograd.Function):
         B, N, Fi = x.shape
         assert adj.shape == (B, N, N), "adj must be [B, N, N]"
         out = torch.empty(B, N, C, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_dense_gatedgraphconv_fwd_workspace_bytes(B, N, C, L)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_dense_gatedgraphconv_fwd", B, N, C, L, device=x.device)
         _call("gcm_dense_gatedgraphconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(w_ih),
               _hip.ptr(w_hh), _hip.ptr(b_ih), _hip.ptr(b_hh), _hip.ptr(out), _hip.ptr(saved), saved_bytes, B, N, Fi,
               C, L, int(add_loop), _hip.stream())
@@ -1204,8 +1200,7 @@ class _DenseGatedGraphConv(torch.autograd.Function):
         g_x = torch.empty(B, N, Fi, device=adj.device, dtype=_f32) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
         g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh = _gated_grads(ctx, weight, w_ih, 2)
-        ws_bytes = _hip.lib().gcm_dense_gatedgraphconv_bwd_workspace_bytes(B, N, C, L)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=adj.device)
+        ws, ws_bytes = _scratch("gcm_dense_gatedgraphconv_bwd", B, N, C, L, device=adj.device)
         _call("gcm_dense_gatedgraphconv_bwd", _hip.ptr(g_out), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(w_ih),
               _hip.ptr(w_hh), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_weight), _hip.ptr(g_w_ih), _hip.ptr(g_w_hh),
               _hip.ptr(g_b_ih), _hip.ptr(g_b_hh), _hip.ptr(g_adj), _hip.ptr(ws), ws_bytes, B, N, Fi, C, L,
@@ -1224,14 +1219,13 @@ class _CsrGatedGraphConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_edge, weight, w_ih, w_hh, b_ih, b_hh, graph):
         x = x.contiguous()
-        w_edge = None if w_edge is None else w_edge.contiguous()
+        w_edge = _contig(w_edge)
         weight, w_ih, w_hh, b_ih, b_hh, L, C = _gated_operands(weight, w_ih, w_hh, b_ih, b_hh)
         _hip.on_device(x, w_edge, weight, w_ih, w_hh, b_ih, b_hh)
         M, Fi = x.shape
         assert M == graph.M and (w_edge is None or w_edge.numel() == graph.E)
         out = torch.empty(M, C, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_csr_gatedgraphconv_fwd_workspace_bytes(M, graph.E, C, L)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_csr_gatedgraphconv_fwd", M, graph.E, C, L, device=x.device)
         _call("gcm_csr_gatedgraphconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(w_edge), _hip.ptr(weight), _hip.ptr(w_ih), _hip.ptr(w_hh), _hip.ptr(b_ih), _hip.ptr(b_hh),
               _hip.ptr(out), _hip.ptr(saved), saved_bytes, M, graph.E, Fi, C, L, _hip.stream())
@@ -1247,14 +1241,11 @@ class _CsrGatedGraphConv(torch.autograd.Function):
         need_x, need_we = ctx.needs_input_grad[:2]
         need_we = need_we and w_edge is not None
         g_out = g_out.contiguous()
-        col_ptr = rows = perm = None
-        if E > 0:
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, E > 0)
         g_x = torch.empty(M, Fi, device=g_out.device, dtype=_f32) if need_x else None
         g_we = torch.zeros_like(w_edge) if need_we else None
         g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh = _gated_grads(ctx, weight, w_ih, 2)
-        ws_bytes = _hip.lib().gcm_csr_gatedgraphconv_bwd_workspace_bytes(M, E, C, L)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g_out.device)
+        ws, ws_bytes = _scratch("gcm_csr_gatedgraphconv_bwd", M, E, C, L, device=g_out.device)
         _call("gcm_csr_gatedgraphconv_bwd", _hip.ptr(g_out), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_edge), _hip.ptr(weight), _hip.ptr(w_ih),
               _hip.ptr(w_hh), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_weight), _hip.ptr(g_w_ih), _hip.ptr(g_w_hh),
@@ -1277,15 +1268,14 @@ class _DenseTagConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, weight, bias, normalize, add_loop):
         x, adj, weight = x.contiguous(), adj.contiguous(), weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        bias = _contig(bias)
         _hip.on_device(x, adj, weight, bias)
         B, N, Fi = x.shape
         K, Fo = weight.shape[0] - 1, weight.shape[1]
         assert adj.shape == (B, N, N), "adj must be [B, N, N]"
         assert weight.shape == (K + 1, Fo, Fi) and (bias is None or bias.numel() == Fo)
         out = torch.empty(B, N, Fo, device=x.device, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_dense_tagconv_fwd_workspace_bytes(B, N, Fi, K)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=x.device)
+        saved, saved_bytes = _scratch("gcm_dense_tagconv_fwd", B, N, Fi, K, device=x.device)
         _call("gcm_dense_tagconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out),
               _hip.ptr(saved), saved_bytes, B, N, Fi, Fo, K, int(normalize), int(add_loop), _hip.stream())
         ctx.save_for_backward(x, adj, weight, saved)
@@ -1303,8 +1293,7 @@ class _DenseTagConv(torch.autograd.Function):
         g_adj = torch.empty_like(adj) if need_adj else None
         g_w = torch.empty_like(weight) if need_w else None
         g_b = torch.empty(Fo, device=x.device, dtype=_f32) if need_b else None
-        ws_bytes = _hip.lib().gcm_dense_tagconv_bwd_workspace_bytes(B, N, Fi, Fo, K)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = _scratch("gcm_dense_tagconv_bwd", B, N, Fi, Fo, K, device=x.device)
         _call("gcm_dense_tagconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(weight), _hip.ptr(saved),
               _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, K,
               ctx.flags[0], ctx.flags[1], _hip.stream())
@@ -1322,8 +1311,8 @@ class _CsrTagConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_edge, weight, bias, graph, normalize):
         x, weight = x.contiguous(), weight.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        w_edge = None if w_edge is None else w_edge.contiguous()
+        bias = _contig(bias)
+        w_edge = _contig(w_edge)
         _hip.on_device(x, w_edge, weight, bias)
         M, Fi = x.shape
         K, Fo = weight.shape[0] - 1, weight.shape[1]
@@ -1331,17 +1320,9 @@ class _CsrTagConv(torch.autograd.Function):
         assert M == graph.M and (w_edge is None or w_edge.numel() == E)
         assert weight.shape == (K + 1, Fo, Fi) and (bias is None or bias.numel() == Fo)
         dev = x.device
-        dst = graph.dst_csr()
-        coef = torch.empty(E, device=dev, dtype=_f32)
-        dinv = torch.empty(M, device=dev, dtype=_f32)
-        loops = torch.empty(2, M, device=dev, dtype=_f32)      # gcn_norm's loop terms: none are added here
-        loop_e = torch.empty(M, device=dev, dtype=_i64)
-        _call("gcm_gcn_norm", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(w_edge),
-              _hip.ptr(coef), _hip.ptr(dinv), _hip.ptr(loops[0]), _hip.ptr(loops[1]), _hip.ptr(loop_e), M, E,
-              int(normalize), 0, 0.0, _hip.stream())
+        dst, coef, dinv, _, _, _ = _gcn_norm(graph, w_edge, normalize, 0, 0.0)     # no loop terms are added here
         out = torch.empty(M, Fo, device=dev, dtype=_f32)
-        saved_bytes = _hip.lib().gcm_csr_tagconv_fwd_workspace_bytes(M, Fi, K)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        saved, saved_bytes = _scratch("gcm_csr_tagconv_fwd", M, Fi, K, device=dev)
         _call("gcm_csr_tagconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(coef),
               _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(saved), saved_bytes, M, E, Fi, Fo, K,
               _hip.stream())
@@ -1360,15 +1341,12 @@ class _CsrTagConv(torch.autograd.Function):
         need_we = need_we and ctx.has_w
         g_out = g_out.contiguous()
         dev = x.device
-        col_ptr = rows = perm = None
-        if (need_x or need_we) and E > 0:
-            col_ptr, rows, perm = graph.csc()
+        col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_we) and E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_we = torch.zeros(E, device=dev, dtype=_f32) if need_we else None
         g_w = torch.empty_like(weight) if need_w else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = _hip.lib().gcm_csr_tagconv_bwd_workspace_bytes(M, E, Fi, Fo, K)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_csr_tagconv_bwd", M, E, Fi, Fo, K, device=dev)
         _call("gcm_csr_tagconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
               _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(coef), _hip.ptr(dinv),
               _hip.ptr(weight), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_we), _hip.ptr(g_w), _hip.ptr(g_b),
@@ -1392,8 +1370,8 @@ class _DenseAggrConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj, w_rel, w_root, bias, aggr):
         x, adj, w_rel = x.contiguous(), adj.contiguous(), w_rel.contiguous()
-        w_root = None if w_root is None else w_root.contiguous()
-        bias = None if bias is None else bias.contiguous()
+        w_root = _contig(w_root)
+        bias = _contig(bias)
         _hip.on_device(x, adj, w_rel, w_root, bias)
         B, N, Fi = x.shape
         Fo = w_rel.shape[0]
@@ -1431,8 +1409,7 @@ class _DenseAggrConv(torch.autograd.Function):
         g_wrel = torch.empty_like(w_rel) if need_wrel else None
         g_wroot = torch.empty_like(w_root) if need_wroot else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = _hip.lib().gcm_dense_aggrconv_bwd_workspace_bytes(B, N, Fi, Fo)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_dense_aggrconv_bwd", B, N, Fi, Fo, device=dev)
         _call("gcm_dense_aggrconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_rel), _hip.ptr(w_root),
               _hip.ptr(agg), _hip.ptr(deg), _hip.ptr(dinv), _hip.ptr(winner), _hip.ptr(g_x), _hip.ptr(g_adj),
               _hip.ptr(g_wrel), _hip.ptr(g_wroot), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, ctx.aggr,
@@ -1451,9 +1428,9 @@ class _CsrAggrConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_edge, w_rel, w_root, bias, graph, aggr):
         x, w_rel = x.contiguous(), w_rel.contiguous()
-        w_root = None if w_root is None else w_root.contiguous()
-        bias = None if bias is None else bias.contiguous()
-        w_edge = None if w_edge is None else w_edge.contiguous()
+        w_root = _contig(w_root)
+        bias = _contig(bias)
+        w_edge = _contig(w_edge)
         _hip.on_device(x, w_edge, w_rel, w_root, bias)
         M, Fi = x.shape
         Fo = w_rel.shape[0]
@@ -1484,17 +1461,15 @@ class _CsrAggrConv(torch.autograd.Function):
         need_we = need_we and w_edge is not None
         g_out = g_out.contiguous()
         dev = x.device
-        col_ptr = rows = perm = dst = None
-        if (need_x or need_we) and E > 0:
-            col_ptr, rows, perm = graph.csc()
-            dst = graph.dst_csr()
+        wanted = (need_x or need_we) and E > 0
+        col_ptr, rows, perm = _csc_or_none(graph, wanted)
+        dst = graph.dst_csr() if wanted else None
         g_x = torch.empty_like(x) if need_x else None
         g_we = torch.zeros_like(w_edge) if need_we else None
         g_wrel = torch.empty_like(w_rel) if need_wrel else None
         g_wroot = torch.empty_like(w_root) if need_wroot else None
         g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
-        ws_bytes = _hip.lib().gcm_csr_aggrconv_bwd_workspace_bytes(M, E, Fi, Fo)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = _scratch("gcm_csr_aggrconv_bwd", M, E, Fi, Fo, device=dev)
         _call("gcm_csr_aggrconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(agg), _hip.ptr(graph.row_ptr),
               _hip.ptr(graph.col), _hip.ptr(dst), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_edge),
               _hip.ptr(winner), _hip.ptr(w_rel), _hip.ptr(w_root), _hip.ptr(g_x), _hip.ptr(g_we), _hip.ptr(g_wrel),

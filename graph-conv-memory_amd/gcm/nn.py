@@ -41,30 +41,52 @@ def _dense_inputs(x, adj):
     return x, adj
 
 
+def _masked(out, mask, x):
+    return out if mask is None else out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+
+
+def _graph_of(x, edge_index, layer=None):
+    """The index SparseGCM attached (`edge_index.gcm_graph`) when it fits x, else one built here on the device.
+    With `layer` named, a masked index is refused."""
+    graph = getattr(edge_index, "gcm_graph", None)
+    if graph is None or graph.M != x.shape[0]:
+        graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
+    if layer is not None and graph.mask is not None:
+        raise ValueError(f"{layer} does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+    return graph
+
+
+def _csr_weights(edge_weight, graph):
+    """GraphConv's rules for edge weights, in CSR order.  PyG: a weight vector of the wrong length is ignored.  Unit
+    weights without a gradient (what SparseGCM passes unless a learned selector is in play: sparse_gcm.py:160-164)
+    multiply by exactly 1: the kernels then skip the weight loads altogether."""
+    w = edge_weight
+    if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
+        return None
+    if w is not None and graph.csr_perm is not None:
+        w = w[graph.csr_perm]
+    return w
+
+
+def _no_attention_dropout(conv):
+    if conv.training and conv.dropout > 0:
+        raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
+
+
 def _dense_aggr(x, adj, mask, w_rel, w_root, bias, aggr):
     """The mean / max form of DenseGraphConv and DenseSAGEConv (csrc/aggrconv.hip).  Max reads only the
     pattern of adj, which then gets no gradient."""
     x, adj = _dense_inputs(x, adj)
     _hip.on_device(w_rel)
     out = _ops.dense_aggrconv(x, adj.detach() if aggr == "max" else adj, w_rel, w_root, bias, aggr)
-    if mask is not None:
-        out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-    return out
+    return _masked(out, mask, x)
 
 
 def _sparse_aggr(x, edge_index, edge_weight, w_rel, w_root, bias, aggr, name):
     """The mean / max form of GraphConv and SAGEConv (csrc/aggrconv.hip)."""
     _hip.on_device(x, w_rel)        # a CPU call fails here, before the index is built
-    graph = getattr(edge_index, "gcm_graph", None)
-    if graph is None or graph.M != x.shape[0]:
-        graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-    if graph.mask is not None:
-        raise ValueError(f"{name} does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
-    w = edge_weight
-    if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
-        w = None        # as GraphConv's sum: a wrong-length vector is ignored, unit weights are not loaded
-    if w is not None and graph.csr_perm is not None:
-        w = w[graph.csr_perm]
+    graph = _graph_of(x, edge_index, name)
+    w = _csr_weights(edge_weight, graph)
     return _ops.csr_aggrconv(x, w, w_rel, w_root, bias, graph, aggr)
 
 
@@ -93,20 +115,12 @@ class DenseGraphConv(torch.nn.Module):
             if _act != _hip.ACT_NONE:
                 raise ValueError("activation fusion is available for aggr='add' only")
             return _dense_aggr(x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_rel.bias, self.aggr)
-        squeeze = x.dim() == 2
-        x = x.unsqueeze(0) if x.dim() == 2 else x
-        adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
-        if adj.dtype != torch.float32:
-            raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
-        if adj.shape[0] != x.shape[0]:
-            adj = adj.expand(x.shape[0], -1, -1)
+        x, adj = _dense_inputs(x, adj)
         if mask is not None and _act != _hip.ACT_NONE:
             raise ValueError("activation fusion is not available together with a mask")
         out = _ops.dense_graphconv(x, adj, self.lin_rel.weight, self.lin_rel.bias,
                                    self.lin_root.weight, _act)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
@@ -141,17 +155,8 @@ class GraphConv(torch.nn.Module):
                 raise ValueError("activation fusion is available for aggr='add' only")
             return _sparse_aggr(x, edge_index, edge_weight, self.lin_rel.weight, self.lin_root.weight,
                                 self.lin_rel.bias, self.aggr, "GraphConv(aggr='%s')" % self.aggr)
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        w = edge_weight
-        if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
-            # PyG: a weight vector of the wrong length is ignored.  Unit weights without a gradient
-            # (what SparseGCM passes unless a learned selector is in play: sparse_gcm.py:160-164) multiply
-            # by exactly 1: the kernel then skips the weight loads altogether
-            w = None
-        if w is not None and graph.csr_perm is not None:
-            w = w[graph.csr_perm]
+        graph = _graph_of(x, edge_index)
+        w = _csr_weights(edge_weight, graph)
         return _ops.csr_graphconv(x, w, self.lin_rel.weight, self.lin_rel.bias,
                                   self.lin_root.weight, graph, _act)
 
@@ -244,16 +249,9 @@ class DenseGCNConv(torch.nn.Module):
         _glorot_zero(self.lin, self.bias)
 
     def forward(self, x, adj, mask=None, add_loop=True):
-        x = x.unsqueeze(0) if x.dim() == 2 else x
-        adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
-        if adj.dtype != torch.float32:
-            raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
-        if adj.shape[0] != x.shape[0]:
-            adj = adj.expand(x.shape[0], -1, -1)
+        x, adj = _dense_inputs(x, adj)
         out = _ops.dense_gcnconv(x, adj, self.lin.weight, self.bias, add_loop, 2.0 if self.improved else 1.0)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
@@ -285,15 +283,8 @@ class GCNConv(torch.nn.Module):
         w = edge_weight
         if w is not None and w.numel() != edge_index.shape[1]:
             raise ValueError(f"edge_weight has {w.numel()} entries for {edge_index.shape[1]} edges")
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("GCNConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
-        if w is not None and getattr(w, "gcm_unit_weights", False):
-            w = None     # unit weights without a gradient: the kernels count 1 per edge
-        if w is not None and graph.csr_perm is not None:
-            w = w[graph.csr_perm]
+        graph = _graph_of(x, edge_index, "GCNConv")
+        w = _csr_weights(w, graph)     # unit weights without a gradient: the kernels count 1 per edge
         return _ops.csr_gcnconv(x, w, self.lin.weight, self.bias, graph, self.normalize,
                                 self.add_self_loops, 2.0 if self.improved else 1.0)
 
@@ -340,9 +331,7 @@ class DenseGINConv(torch.nn.Module):
         x, adj = _dense_inputs(x, adj)
         h = _ops.dense_gin_aggregate(x, adj, self.eps, add_loop)
         out = self.nn(h)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}(nn={self.nn})"
@@ -366,11 +355,7 @@ class GINConv(torch.nn.Module):
 
     def forward(self, x, edge_index):
         _hip.on_device(x, self.eps)     # a CPU call fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("GINConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        graph = _graph_of(x, edge_index, "GINConv")
         return self.nn(_ops.csr_gin_aggregate(x, self.eps, graph))
 
     def __repr__(self):
@@ -402,11 +387,6 @@ def _gat_reset(conv):
         torch.nn.init.zeros_(conv.bias)
 
 
-def _gat_dropout(conv):
-    if conv.training and conv.dropout > 0:
-        raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
-
-
 class DenseGATConv(torch.nn.Module):
     """PyG's DenseGATConv (GAT v1): adj[b,i,j] != 0 means i attends to j (only the pattern matters; the
     diagonal is set when add_loop); y = x W^T viewed [B,N,H,C], e_ij = leaky_relu(<y_i, att_dst> +
@@ -428,18 +408,11 @@ class DenseGATConv(torch.nn.Module):
         _gat_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=True):
-        _gat_dropout(self)
-        x = x.unsqueeze(0) if x.dim() == 2 else x
-        adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
-        if adj.dtype != torch.float32:
-            raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
-        if adj.shape[0] != x.shape[0]:
-            adj = adj.expand(x.shape[0], -1, -1)
+        _no_attention_dropout(self)
+        x, adj = _dense_inputs(x, adj)
         out = _ops.dense_gatconv(x, adj.detach(), self.lin.weight, self.att_src, self.att_dst, self.bias,
                                  self.heads, self.concat, add_loop, self.negative_slope)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
@@ -470,13 +443,9 @@ class GATConv(torch.nn.Module):
     def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None):
         if return_attention_weights is not None:
             raise NotImplementedError("GATConv(return_attention_weights=...) is not implemented")
-        _gat_dropout(self)
+        _no_attention_dropout(self)
         _hip.on_device(self.lin.weight)     # a CPU module fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("GATConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
+        graph = _graph_of(x, edge_index, "GATConv")
         return _ops.csr_gatconv(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
                                 self.concat, self.add_self_loops, self.negative_slope)
 
@@ -521,11 +490,6 @@ def _transformer_operands(conv):
     return w_all, b_all, (conv.lin_beta.weight.view(-1) if conv.beta else None)
 
 
-def _transformer_dropout(conv):
-    if conv.training and conv.dropout > 0:
-        raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
-
-
 class DenseTransformerConv(torch.nn.Module):
     """The dense form of PyG's TransformerConv: adj[b,i,j] != 0 means i attends to j (only the pattern matters; the
     diagonal counts as set when add_loop, which defaults to False so that dense and sparse agree on one edge set).
@@ -547,15 +511,13 @@ class DenseTransformerConv(torch.nn.Module):
         _transformer_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=False):
-        _transformer_dropout(self)
+        _no_attention_dropout(self)
         x, adj = _dense_inputs(x, adj)
         _hip.on_device(self.lin_query.weight)
         w_all, b_all, w_beta = _transformer_operands(self)
         out = _ops.dense_transformerconv(x, adj.detach(), w_all, b_all, w_beta, self.heads, self.concat,
                                          self.root_weight, add_loop)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
@@ -587,14 +549,9 @@ class TransformerConv(torch.nn.Module):
     def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None):
         if return_attention_weights is not None:
             raise NotImplementedError("TransformerConv(return_attention_weights=...) is not implemented")
-        _transformer_dropout(self)
+        _no_attention_dropout(self)
         _hip.on_device(self.lin_query.weight)     # a CPU module fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("TransformerConv does not take a masked GraphIndex (k-hop subgraphs reach it "
-                             "relabelled)")
+        graph = _graph_of(x, edge_index, "TransformerConv")
         w_all, b_all, w_beta = _transformer_operands(self)
         return _ops.csr_transformerconv(x, w_all, b_all, w_beta, graph, self.heads, self.concat, self.root_weight)
 
@@ -661,9 +618,7 @@ class DenseResGatedGraphConv(torch.nn.Module):
         _hip.on_device(self.lin_key.weight)
         w_all, b_all = _resgated_operands(self)
         out = _ops.dense_resgatedconv(x, adj, w_all, b_all, self.bias, self.root_weight, add_loop)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
@@ -692,12 +647,7 @@ class ResGatedGraphConv(torch.nn.Module):
 
     def forward(self, x, edge_index, edge_attr=None):
         _hip.on_device(self.lin_key.weight)     # a CPU call fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("ResGatedGraphConv does not take a masked GraphIndex (k-hop subgraphs reach it "
-                             "relabelled)")
+        graph = _graph_of(x, edge_index, "ResGatedGraphConv")
         w_all, b_all = _resgated_operands(self)
         return _ops.csr_resgatedconv(x, w_all, b_all, self.bias, graph, self.root_weight)
 
@@ -755,9 +705,7 @@ class DenseGatedGraphConv(torch.nn.Module):
         _gated_width(self, x)
         _hip.on_device(self.weight)
         out = _ops.dense_gatedgraphconv(x, adj, self.weight, *_gated_cell(self), add_loop)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"
@@ -786,17 +734,8 @@ class GatedGraphConv(torch.nn.Module):
     def forward(self, x, edge_index, edge_weight=None):
         _gated_width(self, x)
         _hip.on_device(x, self.weight)     # a CPU call fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("GatedGraphConv does not take a masked GraphIndex (k-hop subgraphs reach it "
-                             "relabelled)")
-        w = edge_weight
-        if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
-            w = None        # as GraphConv: a wrong-length vector is ignored, unit weights are not loaded
-        if w is not None and graph.csr_perm is not None:
-            w = w[graph.csr_perm]
+        graph = _graph_of(x, edge_index, "GatedGraphConv")
+        w = _csr_weights(edge_weight, graph)
         return _ops.csr_gatedgraphconv(x, w, self.weight, *_gated_cell(self), graph)
 
     def __repr__(self):
@@ -852,9 +791,7 @@ class DenseTAGConv(torch.nn.Module):
         x, adj = _dense_inputs(x, adj)
         _hip.on_device(self.lins[0].weight)
         out = _ops.dense_tagconv(x, adj, _tag_weight(self), self.bias, self.normalize, add_loop)
-        if mask is not None:
-            out = out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
-        return out
+        return _masked(out, mask, x)
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, K={self.K})"
@@ -883,16 +820,8 @@ class TAGConv(torch.nn.Module):
 
     def forward(self, x, edge_index, edge_weight=None):
         _hip.on_device(x, self.lins[0].weight)     # a CPU call fails here, before the index is built
-        graph = getattr(edge_index, "gcm_graph", None)
-        if graph is None or graph.M != x.shape[0]:
-            graph = _ops.GraphIndex.from_edge_index(edge_index, x.shape[0])
-        if graph.mask is not None:
-            raise ValueError("TAGConv does not take a masked GraphIndex (k-hop subgraphs reach it relabelled)")
-        w = edge_weight
-        if w is not None and (w.numel() != graph.E or getattr(w, "gcm_unit_weights", False)):
-            w = None        # as GraphConv: a wrong-length vector is ignored, unit weights are not loaded
-        if w is not None and graph.csr_perm is not None:
-            w = w[graph.csr_perm]
+        graph = _graph_of(x, edge_index, "TAGConv")
+        w = _csr_weights(edge_weight, graph)
         return _ops.csr_tagconv(x, w, _tag_weight(self), self.bias, graph, self.normalize)
 
     def __repr__(self):
