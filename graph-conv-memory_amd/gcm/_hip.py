@@ -42,6 +42,10 @@ RESGATED_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_resgated.h"))
 GATED_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gated.h"))
 # and the section from gcm_hip_tag.h (TAGConv / DenseTAGConv)
 TAG_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_tag.h"))
+# and the section from gcm_hip_pna.h (PNAConv / DensePNAConv)
+_PNA_HEADER = _abi.header("gcm_hip_pna.h")
+PNA_PROTOTYPES = _abi.prototypes(_PNA_HEADER)
+_CONSTANTS.update(_abi.constants(_PNA_HEADER))
 globals().update({name[4:]: value for name, value in _CONSTANTS.items()})   # GCM_ACT_TANH -> ACT_TANH, ...
 GCM_EUNSUPPORTED = _CONSTANTS["GCM_EUNSUPPORTED"]
 DIR = {d: _CONSTANTS["GCM_DIR_" + d.upper()] for d in ("forward", "backward", "both")}
@@ -86,6 +90,7 @@ def lib():
         bind(handle, RESGATED_PROTOTYPES)
         bind(handle, GATED_PROTOTYPES)
         bind(handle, TAG_PROTOTYPES)
+        bind(handle, PNA_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

@@ -1481,6 +1481,142 @@ def csr_aggrconv(x, w_edge, w_rel, w_root, bias, graph, aggr):
     return _CsrAggrConv.apply(x, w_edge, w_rel, w_root, bias, graph, AGGR[aggr])
 
 
+# ---------------------------------------------------------------------------
+# PNAConv / DensePNAConv (csrc/pnaconv.hip)
+# ---------------------------------------------------------------------------
+PNA_AGGREGATORS = {"sum": _hip.PNA_SUM, "mean": _hip.PNA_MEAN, "min": _hip.PNA_MIN, "max": _hip.PNA_MAX,
+                   "var": _hip.PNA_VAR, "std": _hip.PNA_STD}
+PNA_SCALERS = {"identity": _hip.PNA_IDENTITY, "amplification": _hip.PNA_AMPLIFICATION,
+               "attenuation": _hip.PNA_ATTENUATION, "linear": _hip.PNA_LINEAR,
+               "inverse_linear": _hip.PNA_INVERSE_LINEAR}
+
+
+def _pna_codes(names, table):
+    """The list's codes packed 3 bits each from bit 0, as the C ABI takes them."""
+    return sum(table[n] << (3 * i) for i, n in enumerate(names))
+
+
+class PNAConfig:
+    """What the kernels need to know of a PNA layer besides its tensors."""
+
+    def __init__(self, in_channels, out_channels, towers, divide_input, aggregators, scalers):
+        self.cin, self.cout, self.T, self.divide = in_channels, out_channels, towers, int(divide_input)
+        self.A, self.S = len(aggregators), len(scalers)
+        self.aggrs, self.scalers = _pna_codes(aggregators, PNA_AGGREGATORS), _pna_codes(scalers, PNA_SCALERS)
+        self.Fi = in_channels // towers if divide_input else in_channels
+        self.K1 = (1 + self.A * self.S) * self.Fi
+        self.need_var = any(a in ("var", "std") for a in aggregators)
+        self.need_mm = any(a in ("min", "max") for a in aggregators)
+
+    def dims(self):
+        return self.cin, self.cout, self.T, self.divide
+
+    def lists(self):
+        return self.aggrs, self.A, self.scalers, self.S
+
+
+def _pna_saved(cfg, rows, dev, winner_dtype, has_lin):
+    """What the forward keeps for the backward: ab, cat, h, cnt, stat, winner (None where the layer has no use)."""
+    C = cfg.T * cfg.Fi
+    ab = torch.empty(rows, 2 * C, device=dev, dtype=_f32)
+    cat = torch.empty(rows, cfg.T * cfg.K1, device=dev, dtype=_f32)
+    h = torch.empty(rows, cfg.cout, device=dev, dtype=_f32) if has_lin else None
+    cnt = torch.empty(rows, device=dev, dtype=torch.int32)
+    stat = torch.empty(rows, 2 * C, device=dev, dtype=_f32) if cfg.need_var else None
+    winner = torch.empty(rows, 2 * C, device=dev, dtype=winner_dtype) if cfg.need_mm else None
+    return ab, cat, h, cnt, stat, winner
+
+
+def _pna_grads(ctx, operands):
+    """Empty gradients for (x, w_pre, b_pre, w_post, b_post, w_lin, b_lin) where they are asked for."""
+    return [torch.empty_like(t) if t is not None and need else None
+            for t, need in zip(operands, ctx.needs_input_grad)]
+
+
+class _DensePNAConv(torch.autograd.Function):
+    """x [B,N,in], adj [B,N,N] (pattern only: no gradient); the operands stacked by tower as include/gcm_hip_pna.h
+    lays them out; w_lin / b_lin None: the output is h (the towers' post linears side by side)."""
+
+    @staticmethod
+    def forward(ctx, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, adj, cfg, add_loop):
+        x, adj = x.contiguous(), adj.contiguous()
+        w_pre, b_pre, w_post, b_post = (t.contiguous() for t in (w_pre, b_pre, w_post, b_post))
+        w_lin, b_lin = _contig(w_lin), _contig(b_lin)
+        _hip.on_device(x, adj, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg)
+        B, N, cin = x.shape
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert cin == cfg.cin, f"x has {cin} channels, the layer takes {cfg.cin}"
+        dev = x.device
+        out = torch.empty(B, N, cfg.cout, device=dev, dtype=_f32)
+        saved = _pna_saved(cfg, B * N, dev, torch.int16, w_lin is not None)
+        _call("gcm_dense_pnaconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_pre), _hip.ptr(b_pre), _hip.ptr(w_post),
+              _hip.ptr(b_post), _hip.ptr(w_lin), _hip.ptr(b_lin), _hip.ptr(avg_deg), _hip.ptr(out),
+              *[_hip.ptr(t) for t in saved], B, N, *cfg.dims(), *cfg.lists(), int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, adj, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, *saved)
+        ctx.cfg, ctx.add_loop = cfg, int(add_loop)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, ab, cat, h, cnt, stat, winner = ctx.saved_tensors
+        cfg = ctx.cfg
+        B, N, _ = x.shape
+        g_out = g_out.contiguous()
+        grads = _pna_grads(ctx, (x, w_pre, b_pre, w_post, b_post, w_lin, b_lin))
+        ws, ws_bytes = _scratch("gcm_dense_pnaconv_bwd", B, N, *cfg.dims(), cfg.A, cfg.S, device=x.device)
+        _call("gcm_dense_pnaconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_pre), _hip.ptr(w_post),
+              _hip.ptr(w_lin), _hip.ptr(avg_deg), _hip.ptr(ab), _hip.ptr(cat), _hip.ptr(h), _hip.ptr(cnt),
+              _hip.ptr(stat), _hip.ptr(winner), *[_hip.ptr(g) for g in grads], _hip.ptr(ws), ws_bytes, B, N,
+              *cfg.dims(), *cfg.lists(), ctx.add_loop, _hip.stream())
+        return (*grads, None, None, None, None)
+
+
+def dense_pnaconv(x, adj, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, cfg, add_loop):
+    return _DensePNAConv.apply(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, adj, cfg, add_loop)
+
+
+class _CsrPNAConv(torch.autograd.Function):
+    """x [M,in]; every CSR entry of `graph` is one message."""
+
+    @staticmethod
+    def forward(ctx, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, cfg):
+        x = x.contiguous()
+        w_pre, b_pre, w_post, b_post = (t.contiguous() for t in (w_pre, b_pre, w_post, b_post))
+        w_lin, b_lin = _contig(w_lin), _contig(b_lin)
+        _hip.on_device(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg)
+        M, cin = x.shape
+        assert M == graph.M
+        assert cin == cfg.cin, f"x has {cin} channels, the layer takes {cfg.cin}"
+        dev = x.device
+        out = torch.empty(M, cfg.cout, device=dev, dtype=_f32)
+        saved = _pna_saved(cfg, M, dev, torch.int32, w_lin is not None)
+        _call("gcm_csr_pnaconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(w_pre),
+              _hip.ptr(b_pre), _hip.ptr(w_post), _hip.ptr(b_post), _hip.ptr(w_lin), _hip.ptr(b_lin), _hip.ptr(avg_deg),
+              _hip.ptr(out), *[_hip.ptr(t) for t in saved], M, graph.E, *cfg.dims(), *cfg.lists(), _hip.stream())
+        ctx.save_for_backward(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, *saved)
+        ctx.cfg, ctx.graph = cfg, graph
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, ab, cat, h, cnt, stat, winner = ctx.saved_tensors
+        cfg, graph = ctx.cfg, ctx.graph
+        M, E = graph.M, graph.E
+        g_out = g_out.contiguous()
+        grads = _pna_grads(ctx, (x, w_pre, b_pre, w_post, b_post, w_lin, b_lin))
+        col_ptr, rows, perm = _csc_or_none(graph, E > 0 and any(g is not None for g in grads[:3]))
+        ws, ws_bytes = _scratch("gcm_csr_pnaconv_bwd", M, E, *cfg.dims(), cfg.A, cfg.S, device=x.device)
+        _call("gcm_csr_pnaconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm),
+              _hip.ptr(w_pre), _hip.ptr(w_post), _hip.ptr(w_lin), _hip.ptr(avg_deg), _hip.ptr(ab), _hip.ptr(cat),
+              _hip.ptr(h), _hip.ptr(cnt), _hip.ptr(stat), _hip.ptr(winner), *[_hip.ptr(g) for g in grads], _hip.ptr(ws),
+              ws_bytes, M, E, *cfg.dims(), *cfg.lists(), _hip.stream())
+        return (*grads, None, None, None)
+
+
+def csr_pnaconv(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, cfg):
+    return _CsrPNAConv.apply(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, cfg)
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

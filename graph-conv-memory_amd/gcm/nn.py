@@ -828,6 +828,194 @@ class TAGConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, K={self.K})"
 
 
+def degree_histogram(adj_or_edge_index, num_nodes=None):
+    """The `deg` argument of PNAConv / DensePNAConv from a graph at hand (a memory user has no dataset loader to take
+    it from: a rollout's final adjacency will do): a LongTensor whose entry d is the number of nodes with in-degree d.
+    An integer tensor [2,E] is an edge list (source, sink) over num_nodes nodes (default: the largest index + 1); any
+    other tensor is an adjacency [N,N] or [B,N,N] whose row i has one neighbour per non-zero entry.  Plain torch ops."""
+    t = adj_or_edge_index
+    if t.dim() == 2 and t.shape[0] == 2 and not t.is_floating_point() and t.dtype != torch.bool:
+        if num_nodes is None:
+            num_nodes = int(t.max()) + 1 if t.numel() else 0
+        deg = torch.bincount(t[1].reshape(-1), minlength=num_nodes)
+    else:
+        deg = (t != 0).sum(-1).reshape(-1)
+    return torch.bincount(deg)
+
+
+_PNA_ACTS = {"relu": torch.nn.ReLU, "tanh": torch.nn.Tanh, "sigmoid": torch.nn.Sigmoid, "elu": torch.nn.ELU,
+             "leaky_relu": torch.nn.LeakyReLU, "gelu": torch.nn.GELU, "silu": torch.nn.SiLU}
+
+
+class _DegreeScalers(torch.nn.Module):
+    """Holds PyG's `aggr_module.avg_deg_lin` / `aggr_module.avg_deg_log` buffers ([1] each) of a degree histogram."""
+
+    def __init__(self, deg):
+        super().__init__()
+        deg = torch.as_tensor(deg).detach().to("cpu", torch.float64).reshape(-1)     # a histogram from the device too
+        n = float(deg.sum())
+        if n <= 0:
+            raise ValueError("deg must count at least one node")
+        d = torch.arange(deg.numel(), dtype=torch.float64)
+        self.register_buffer("avg_deg_lin", ((d * deg).sum() / n).to(torch.float32).reshape(1))
+        self.register_buffer("avg_deg_log", (((d + 1).log() * deg).sum() / n).to(torch.float32).reshape(1))
+
+
+def _pna_params(conv, name, in_channels, out_channels, aggregators, scalers, deg, towers, pre_layers, post_layers,
+                divide_input, act, act_kwargs, train_norm):
+    if not isinstance(in_channels, int):
+        raise NotImplementedError(f"{name} with a tuple in_channels (bipartite graphs) is not implemented")
+    if pre_layers != 1:
+        raise NotImplementedError(f"{name}(pre_layers={pre_layers}) is not implemented: the kernels rely on a message "
+                                  "that is linear in x_i and x_j (pre_layers=1)")
+    if train_norm:
+        raise NotImplementedError(f"{name}(train_norm=True) is not implemented: the degree statistics are buffers")
+    aggregators, scalers = list(aggregators), list(scalers)
+    for a in aggregators:
+        if a not in _ops.PNA_AGGREGATORS:
+            raise ValueError(f"unknown aggregator '{a}': one of {sorted(_ops.PNA_AGGREGATORS)}")
+    for s in scalers:
+        if s not in _ops.PNA_SCALERS:
+            raise ValueError(f"unknown scaler '{s}': one of {sorted(_ops.PNA_SCALERS)}")
+    if not 1 <= len(aggregators) <= 8 or not 1 <= len(scalers) <= 8:
+        raise ValueError("aggregators and scalers take 1 to 8 names each")
+    if post_layers < 1:
+        raise ValueError(f"post_layers must be at least 1; got {post_layers}")
+    if divide_input:
+        assert in_channels % towers == 0
+    assert out_channels % towers == 0
+    conv.in_channels, conv.out_channels, conv.towers, conv.divide_input = in_channels, out_channels, towers, divide_input
+    conv.aggregators, conv.scalers = aggregators, scalers
+    conv.pre_layers, conv.post_layers = pre_layers, post_layers
+    conv.F_in = in_channels // towers if divide_input else in_channels
+    conv.F_out = out_channels // towers
+    conv.aggr_module = _DegreeScalers(deg)
+    conv.pre_nns, conv.post_nns = torch.nn.ModuleList(), torch.nn.ModuleList()
+    for _ in range(towers):
+        conv.pre_nns.append(torch.nn.Sequential(torch.nn.Linear(2 * conv.F_in, conv.F_in)))
+        mods = [torch.nn.Linear((len(aggregators) * len(scalers) + 1) * conv.F_in, conv.F_out)]
+        for _ in range(post_layers - 1):
+            if isinstance(act, str):
+                if act not in _PNA_ACTS:
+                    raise ValueError(f"unknown activation '{act}': one of {sorted(_PNA_ACTS)} or a module")
+                mods.append(_PNA_ACTS[act](**(act_kwargs or {})))
+            else:
+                mods.append(torch.nn.Identity() if act is None else act)
+            mods.append(torch.nn.Linear(conv.F_out, conv.F_out))
+        conv.post_nns.append(torch.nn.Sequential(*mods))
+    conv.lin = torch.nn.Linear(out_channels, out_channels)
+    conv._cfg = _ops.PNAConfig(in_channels, out_channels, towers, divide_input, aggregators, scalers)
+
+
+def _pna_reset(conv):
+    for nns in (conv.pre_nns, conv.post_nns):
+        for seq in nns:
+            _gin_reset(seq)
+    conv.lin.reset_parameters()
+
+
+def _pna_operands(conv):
+    """(w_pre [T,2Fi,Fi], b_pre [T,2Fi], w_post [T,Fo,K1], b_post [T,Fo], w_lin, b_lin, avg_deg [2]): each tower's pre
+    weight split into its destination and source halves, stacked [dst; src] (the bias pads with zeros for the source
+    half), and the first post linears stacked; autograd hands every Linear its slice of the stacked gradients.  With
+    post_layers > 1 the final linear is not the kernels' (w_lin = b_lin = None)."""
+    Fi = conv.F_in
+    pre = [seq[0] for seq in conv.pre_nns]
+    post = [seq[0] for seq in conv.post_nns]
+    w_pre = torch.stack([torch.cat([lin.weight[:, :Fi], lin.weight[:, Fi:]]) for lin in pre])
+    b_pre = torch.stack([torch.cat([lin.bias, lin.bias.new_zeros(Fi)]) for lin in pre])
+    w_post = torch.stack([lin.weight for lin in post])
+    b_post = torch.stack([lin.bias for lin in post])
+    fused = conv.post_layers == 1
+    agg = conv.aggr_module
+    return (w_pre, b_pre, w_post, b_post, conv.lin.weight if fused else None, conv.lin.bias if fused else None,
+            torch.cat([agg.avg_deg_lin, agg.avg_deg_log]))
+
+
+def _pna_tail(conv, h):
+    """post_layers > 1: what follows each tower's first post linear, and the final linear, as torch modules."""
+    if conv.post_layers == 1:
+        return h
+    Fo = conv.F_out
+    hs = [seq[1:](h[..., t * Fo:(t + 1) * Fo]) for t, seq in enumerate(conv.post_nns)]
+    return conv.lin(torch.cat(hs, -1))
+
+
+_PNA_DOC = """Per tower t (x_t: the tower's in_channels / towers columns of x with divide_input, else all of x): the
+    message of every edge j -> i is m = pre_nns[t]([x_i | x_j]); the aggregators listed - sum, mean, min, max, var =
+    mean(m^2) - mean(m)^2, std = sqrt(clamp(var, 1e-5)) set to 0 where that is <= sqrt(1e-5) - are taken per channel
+    over the n_i messages of i and concatenated in list order; each scaler listed - identity, amplification log(n+1) /
+    avg_deg_log, attenuation avg_deg_log / log(max(n,1)+1), linear n / avg_deg_lin, inverse_linear avg_deg_lin /
+    max(n,1) - multiplies that block, the results concatenated in list order; h_t = post_nns[t]([x_t | scaled]); out =
+    lin(cat_t h_t).  Every aggregator is 0 where n_i = 0; a tie in min / max goes to the first candidate, which alone
+    gets the gradient.  `deg` is the histogram of in-degrees of the training graphs (gcm.nn.degree_histogram makes
+    one): avg_deg_lin = sum d deg[d] / sum deg, avg_deg_log = sum log(d+1) deg[d] / sum deg.  Parameters and buffers
+    carry PyG 2.3+'s names - pre_nns.t.0.{weight [F_in, 2 F_in], bias}, post_nns.t.0.{weight [F_out, (A S + 1) F_in],
+    bias}, post_nns.t.{2,4,..} with post_layers > 1, lin.{weight, bias}, aggr_module.avg_deg_lin / avg_deg_log [1] -
+    a layout written from PyG's source as remembered, which no test here can pin against an installed PyG.  Forward
+    and backward are HIP kernels (csrc/pnaconv.hip): one pass over a neighbourhood produces every statistic, and no
+    per-edge message is stored; with post_layers > 1 what follows each tower's first post linear runs as torch
+    modules.  in_channels, out_channels <= 128 (wider: RuntimeError, code -2); float32.  Not implemented
+    (NotImplementedError): edge_dim, pre_layers != 1, train_norm=True, a tuple in_channels."""
+
+
+class DensePNAConv(torch.nn.Module):
+    __doc__ = """The dense form of PyG's PNAConv (Corso et al., Principal Neighbourhood Aggregation; PyG has no dense
+    twin): adj [B,N,N] float32, adj[b,i,j] != 0 means i aggregates from j; only the pattern is read and adj gets no
+    gradient; add_loop (default False, so that dense and sparse agree on one edge set) sets the diagonal; x [B,N,F];
+    the mask is applied last.  A tie in min / max goes to the lowest j.
+    """ + _PNA_DOC + """  Same parameters as PNAConv: the state_dicts interchange.  Not a DenseGraphConv: DenseGCM
+    runs a stack of these through its layered path."""
+
+    def __init__(self, in_channels, out_channels, aggregators, scalers, deg, towers=1, pre_layers=1, post_layers=1,
+                 divide_input=False, act="relu", act_kwargs=None, train_norm=False):
+        super().__init__()
+        _pna_params(self, "DensePNAConv", in_channels, out_channels, aggregators, scalers, deg, towers, pre_layers,
+                    post_layers, divide_input, act, act_kwargs, train_norm)
+
+    def reset_parameters(self):
+        _pna_reset(self)
+
+    def forward(self, x, adj, mask=None, add_loop=False):
+        x, adj = _dense_inputs(x, adj)
+        _hip.on_device(self.lin.weight)
+        h = _ops.dense_pnaconv(x, adj.detach(), *_pna_operands(self), self._cfg, add_loop)
+        return _masked(_pna_tail(self, h), mask, x)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, towers={self.towers})"
+
+
+class PNAConv(torch.nn.Module):
+    __doc__ = """PyG's PNAConv (Corso et al., Principal Neighbourhood Aggregation; flow source_to_target) without
+    edge features: edge_index [2,E] = (source, sink), x [M,F].  The edges are used as given: no loop is added or
+    removed, duplicates and self loops are separate messages, in CSR order (the edges stably sorted by sink): the
+    first of them wins a tie in min / max.  Uses the `edge_index.gcm_graph` index SparseGCM attaches; any other edge
+    list is indexed here.  edge_attr is accepted and ignored.
+    """ + _PNA_DOC + """  Not a GraphConv: SparseGCM runs a stack of these through its generic path."""
+
+    def __init__(self, in_channels, out_channels, aggregators, scalers, deg, edge_dim=None, towers=1, pre_layers=1,
+                 post_layers=1, divide_input=False, act="relu", act_kwargs=None, train_norm=False):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("PNAConv(edge_dim=...) is not implemented: edge features do not enter the "
+                                      "message")
+        self.edge_dim = edge_dim
+        _pna_params(self, "PNAConv", in_channels, out_channels, aggregators, scalers, deg, towers, pre_layers,
+                    post_layers, divide_input, act, act_kwargs, train_norm)
+
+    def reset_parameters(self):
+        _pna_reset(self)
+
+    def forward(self, x, edge_index, edge_attr=None):
+        _hip.on_device(x, self.lin.weight)     # a CPU call fails here, before the index is built
+        graph = _graph_of(x, edge_index, "PNAConv")
+        return _pna_tail(self, _ops.csr_pnaconv(x, *_pna_operands(self), graph, self._cfg))
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, towers={self.towers})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
