@@ -559,6 +559,67 @@ def sparse_extract(feats, T, taus, node_off, B, t_pad, flags):
     return _SparseExtract.apply(feats, T, taus, node_off, B, t_pad, flags)
 
 
+# ---------------------------------------------------------------------------
+# SparseGCM's sliding window: drop the oldest k_b nodes of every graph (include/gcm_hip_window.h)
+# ---------------------------------------------------------------------------
+class _SparseDropOldest(torch.autograd.Function):
+    """(nodes [B,N,F], values [E]; idx [3,E] coalesced, T [B], k [B]) -> (nodes', idx' [3,E'], values' [E'], T',
+    bptr [B+1]): gcm_sparse_drop_plan, the one readback (E'), gcm_sparse_drop_nodes, gcm_sparse_drop_edges.  New
+    tensors; the inputs are not written.  Gradients reach nodes and values (a row shift and a scatter)."""
+
+    @staticmethod
+    def forward(ctx, nodes, values, idx, T, k):
+        nodes, values, idx = nodes.contiguous(), values.contiguous(), idx.contiguous()
+        T, k = T.contiguous(), k.contiguous()
+        _hip.on_device(nodes, values, idx, T, k)
+        B, N, F = nodes.shape
+        E, dev = idx.shape[1], nodes.device
+        st = _hip.stream()
+        n_chunks = -(-E // _hip.SPARSE_DROP_CHUNK)
+        chunk_off = torch.empty(n_chunks + 1, dtype=_i64, device=dev)
+        T_out = torch.empty_like(T)
+        _call("gcm_sparse_drop_plan", _hip.ptr(idx) if E else None, _hip.ptr(k), _hip.ptr(T), _hip.ptr(T_out),
+              _hip.ptr(chunk_off), E, B, N, st)
+        nodes_out = torch.empty_like(nodes)
+        _call("gcm_sparse_drop_nodes", _hip.ptr(nodes), _hip.ptr(k), _hip.ptr(T), _hip.ptr(nodes_out), B, N, F, 0, st)
+        E_new = int(chunk_off[n_chunks].item()) if E else 0            # the one readback
+        idx_out = torch.empty(3, E_new, dtype=_i64, device=dev)
+        values_out = torch.empty(E_new, dtype=_f32, device=dev)
+        src_pos = torch.empty(E_new, dtype=_i64, device=dev)
+        bptr = torch.empty(B + 1, dtype=_i64, device=dev)
+        _call("gcm_sparse_drop_edges", _hip.ptr(idx) if E else None, _hip.ptr(values) if E_new else None, _hip.ptr(k),
+              _hip.ptr(T), _hip.ptr(chunk_off), _hip.ptr(idx_out) if E_new else None,
+              _hip.ptr(values_out) if E_new else None, _hip.ptr(src_pos) if E_new else None, _hip.ptr(bptr), E, E_new,
+              B, N, st)
+        ctx.save_for_backward(T, k, src_pos)
+        ctx.dims = (B, N, F, E, E_new)
+        ctx.mark_non_differentiable(idx_out, T_out, bptr)
+        return nodes_out, idx_out, values_out, T_out, bptr
+
+    @staticmethod
+    def backward(ctx, g_nodes, _g_idx, g_values, _g_T, _g_bptr):
+        T, k, src_pos = ctx.saved_tensors
+        B, N, F, E, E_new = ctx.dims
+        st = _hip.stream()
+        gn = gv = None
+        if ctx.needs_input_grad[0] and g_nodes is not None:
+            g_nodes = g_nodes.contiguous()
+            gn = torch.empty_like(g_nodes)
+            _call("gcm_sparse_drop_nodes", _hip.ptr(g_nodes), _hip.ptr(k), _hip.ptr(T), _hip.ptr(gn), B, N, F, 1, st)
+        if ctx.needs_input_grad[1] and g_values is not None:
+            g_values = g_values.contiguous()
+            gv = torch.empty(E, dtype=_f32, device=T.device)
+            _call("gcm_sparse_drop_values_bwd", _hip.ptr(g_values) if E_new else None,
+                  _hip.ptr(src_pos) if E_new else None, _hip.ptr(gv) if E else None, E, E_new, st)
+        return gn, gv, None, None, None
+
+
+def sparse_drop_oldest(nodes, idx, values, T, k):
+    """-> (nodes', idx', values', T', bptr): every graph without its oldest min(max(k_b, 0), T_b) nodes."""
+    nodes_out, idx_out, values_out, T_out, bptr = _SparseDropOldest.apply(nodes, values, idx, T, k)
+    return nodes_out, idx_out, values_out, T_out, bptr
+
+
 def _scratch(name, *dims, device):
     """(uint8 tensor, nbytes) of the size the library's `<name>_workspace_bytes(*dims)` asks for: a backward's
     workspace or what a forward saves for its backward."""

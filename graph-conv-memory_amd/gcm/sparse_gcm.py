@@ -34,9 +34,12 @@ class SparseGCM(torch.nn.Module):
         max_hops: Union[int, None] = None,
         positional_encoder: torch.nn.Module = None,
         finite_check: str = "sync",
+        overflow: str = "raise",
     ):
         super().__init__()
         assert finite_check in ("sync", "off")
+        if overflow not in ("raise", "wrap"):
+            raise ValueError(f'overflow must be "raise" or "wrap", got {overflow!r}')
         self.preprocessor = preprocessor
         self.gnn = gnn
         self.graph_size = graph_size
@@ -45,6 +48,11 @@ class SparseGCM(torch.nn.Module):
         self.positional_encoder = positional_encoder
         self.max_hops = max_hops
         self.finite_check = finite_check
+        # "raise": a call that would give a graph more than graph_size nodes raises Exception("Overflow") (the
+        # reference).  "wrap": every graph first loses its oldest max(0, T_b + tau_b - graph_size) nodes
+        # (drop_oldest), like DenseGCM's wrap_overflow - a sliding window over the last graph_size observations.
+        self.overflow = overflow
+        self._full_T = None       # wrap mode: the T a wrapped call returned (some graph full: the next call wraps too)
         self._flags = {}
         self._fast_plan = None    # (structure analysed once): the canonical configuration's C++ host path
         self.fast_host = True     # False: the layered Python path always (A/B tests)
@@ -58,7 +66,7 @@ class SparseGCM(torch.nn.Module):
         """copy.deepcopy / pickle of a module that has already run: the analysed structure, the flag words and
         the stepwise chain are runtime caches (rebuilt on the first call)."""
         d = dict(self.__dict__)
-        d.update(_fast_plan=None, _flags={}, _chain=None)
+        d.update(_fast_plan=None, _flags={}, _chain=None, _full_T=None)
         return d
 
     def get_initial_hidden_state(self, x):
@@ -170,6 +178,57 @@ class SparseGCM(torch.nn.Module):
             self.__dict__["_chain"] = None
         super().__setattr__(name, value)
 
+    def drop_oldest(self, hidden, k):
+        """The hidden state (nodes, adj, T) with the oldest k_b nodes of every graph gone; k int64 [B], clamped per
+        graph into [0, T_b].  nodes'[b, i] = nodes[b, i + k_b] (zero from row T_b - k_b on); an edge (b, sink, source)
+        stays iff source >= k_b and becomes (b, sink - k_b, source - k_b) with its value; survivors keep their order,
+        so the list stays coalesced (no sort); T' = T - k.  Functional: new tensors, the inputs untouched.  Gradients
+        reach the node matrix and the edge values.  Kernels: csrc/sparse_window.hip; one small readback (the new
+        edge count).  The stepwise chain ends here: its caches depend on the dropped nodes."""
+        nodes, adj, T = hidden
+        if not isinstance(k, torch.Tensor) or k.dtype != torch.long:
+            raise TypeError("k must be a torch.int64 tensor, got "
+                            f"{k.dtype if isinstance(k, torch.Tensor) else type(k).__name__}")
+        if tuple(k.shape) != (nodes.shape[0],):
+            raise ValueError(f"k must have shape {[nodes.shape[0]]}, got {list(k.shape)}")
+        return self._drop(nodes, adj, T, k)[:3]
+
+    def _drop(self, nodes, adj, T, k):
+        """-> (nodes', adj', T', the new list's per-graph pointer [B+1])."""
+        if nodes.is_cuda and nodes.device.index != torch.cuda.current_device():
+            with torch.cuda.device(nodes.device):
+                return self._drop(nodes, adj, T, k)
+        if k.device != nodes.device:
+            k = k.to(nodes.device)
+        adj = adj.coalesce()
+        n2, idx, val, T2, bptr = _ops.sparse_drop_oldest(nodes, adj.indices(), adj.values(), T, k)
+        adj2 = torch.sparse_coo_tensor(idx, val, size=adj.shape, is_coalesced=True)
+        adj2.gcm_bptr = bptr
+        self._chain = None
+        return n2, adj2, T2, bptr
+
+    def reset_hidden(self, hidden, mask):
+        """The hidden state with the graphs of `mask` (bool [B], on the device or the CPU) emptied - T = 0, zero rows,
+        no edges - what an RL loop does to the memories of finished episodes: drop_oldest with k = where(mask, T, 0).
+        The gradient w.r.t. a cleared graph's incoming state is zero, the others' the identity."""
+        nodes, adj, T = hidden
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+            raise TypeError("mask must be a torch.bool tensor, got "
+                            f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+        if tuple(mask.shape) != (nodes.shape[0],):
+            raise ValueError(f"mask must have shape {[nodes.shape[0]]}, got {list(mask.shape)}")
+        if mask.device != T.device:
+            mask = mask.to(T.device)
+        return self._drop(nodes, adj, T, torch.where(mask, T, torch.zeros_like(T)))[:3]
+
+    def _wrap(self, nodes, adj, T, taus, N):
+        """overflow="wrap": every graph without the max(0, T_b + tau_b - N) oldest nodes the call has no room for
+        (computed on the device), and DenseGCM's one-time line."""
+        if not SparseGCM.did_warn:
+            print("Overflow detected, wrapping around. Will not warn again")
+            SparseGCM.did_warn = True
+        return self._drop(nodes, adj, T, (T + taus - N).clamp_(min=0))[:3]
+
     def rollout(self, x, hidden=None, taus=None):
         """The time-batched entry (the shape RLlib's wrapper holds: x [B, T, feat], batch first):
         T memory steps of every graph in ONE call - which is what forward() already is for SparseGCM (the reference's
@@ -222,27 +281,48 @@ class SparseGCM(torch.nn.Module):
             except KeyError:       # (parametrized / re-registered weights: the attribute protocol)
                 ws = (c1.lin_rel.weight, c1.lin_rel.bias, c1.lin_root.weight,
                       c2.lin_rel.weight, c2.lin_rel.bias, c2.lin_root.weight)
+            wrap = self.overflow == "wrap" and not lazy
+            wrapped = False
+            if wrap and T is self._full_T and t_pad > 0:
+                # the state a wrapped call returned, so some graph is full and (unless its tau is 0) this call
+                # overflows as well: drop first instead of learning it from a failed attempt.  Only a bound - k is
+                # computed on the device from T and taus, and a drop by 0 everywhere is the identity.
+                nodes, adj, T = self._wrap(nodes, adj, T, taus, N)
+                wrapped, fresh, chain = True, False, None
             r = fn(x, taus, nodes, N, adj.indices(), T, hops, ws[0], ws[1], ws[2], a1, ws[3], ws[4], ws[5], a2,
                    flags, chain, fresh, self.finite_check == "sync")
-            if r == 1:                                         # sparse_gcm.py:120-121
+            if r == 1 and wrap and not wrapped:
+                # (the call came back clean: chain dropped, flag word zeroed) drop, then the call as it is
+                nodes, adj, T = self._wrap(nodes, adj, T, taus, N)
+                wrapped = True
+                r = fn(x, taus, nodes, N, adj.indices(), T, hops, ws[0], ws[1], ws[2], a1, ws[3], ws[4], ws[5], a2,
+                       flags, None, False, self.finite_check == "sync")
+            if r == 1:                                         # sparse_gcm.py:120-121 (wrap: some tau_b > N)
                 raise Exception("Overflow")
             mx_dense, nodes_out, idx, vals, T_out, bits = r
+            self._full_T = T_out if wrapped else None
             vals.gcm_unit_weights = True
             adj_out = torch.sparse_coo_tensor(idx, vals, size=adj.shape, is_coalesced=True)
             self._check_flags(flags, bits)      # (bits >= 0: the flag word came back with the call's sizes)
             return mx_dense, (nodes_out, adj_out, T_out)
 
-        node_off, _new_off, totals = _ops.sparse_plan(T, taus)
-        sel, sel_plan = self.edge_selectors, None
-        if hasattr(sel, "plan"):        # a selector that sizes itself on the device: one readback for both
-            edge_off = sel.plan(T, taus)
-            sizes = torch.cat([totals, edge_off[B:]]).tolist()
-            sel_plan = (edge_off, int(sizes[4]))
-        else:
-            sizes = totals.tolist()
-        M, _n_new, max_total, _max_tau = (int(v) for v in sizes[:4])         # the one readback
-        if max_total > N:                                   # sparse_gcm.py:120-121
-            raise Exception("Overflow")
+        sel = self.edge_selectors
+        for attempt in range(2):
+            node_off, _new_off, totals = _ops.sparse_plan(T, taus)
+            sel_plan = None
+            if hasattr(sel, "plan"):        # a selector that sizes itself on the device: one readback for both
+                edge_off = sel.plan(T, taus)
+                sizes = torch.cat([totals, edge_off[B:]]).tolist()
+                sel_plan = (edge_off, int(sizes[4]))
+            else:
+                sizes = totals.tolist()
+            M, _n_new, max_total, max_tau = (int(v) for v in sizes[:4])         # the one readback
+            if max_total <= N:
+                break
+            if self.overflow != "wrap" or attempt or max_tau > N:           # sparse_gcm.py:120-121
+                raise Exception("Overflow")
+            # a call that does not overflow never gets here: drop (max_total came with the readback above), re-plan
+            nodes, adj, T = self._wrap(nodes, adj, T, taus, N)
 
         nodes = _ops.sparse_insert(nodes, x, T, taus, flags)
         user_code = self.preprocessor is not None or self.positional_encoder is not None
