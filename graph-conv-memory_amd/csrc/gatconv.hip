@@ -644,7 +644,9 @@ extern "C" int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int
                                    gcm_stream_t stream) {
   GCM_REQUIRE(g_out && x && row_ptr && w && att_src && att_dst && y && s_src && s_dst && row_m && row_l && workspace);
   GCM_REQUIRE(M > 0 && E >= 0 && Fi > 0 && H > 0 && C > 0);
-  GCM_REQUIRE(E == 0 || (col && col_ptr && rows && perm));
+  // (the CSC view serves g_x / g_w / g_att_*: a bias-only request comes without one)
+  const bool bias_only = !g_x && !g_w && !g_att_src && !g_att_dst;
+  GCM_REQUIRE(E == 0 || (col && (bias_only || (col_ptr && rows && perm))));
   if (unsupported(M, Fi, H, C)) return GCM_EUNSUPPORTED;
   const int Fo = concat ? H * C : C;
   const BwdWs L = bwd_ws(M, M, true, E, Fi, H, C, Fo);
@@ -653,7 +655,7 @@ extern "C" int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int
   char* ws = (char*)workspace;
   int rc;
   if (g_bias && (rc = colsum(g_out, M, Fo, g_bias, (float*)(ws + L.slabs), s))) return rc;
-  if (!g_x && !g_w && !g_att_src && !g_att_dst) return GCM_OK;
+  if (bias_only) return GCM_OK;
   if ((rc = dout(g_out, L, ws, M, H, C, concat, s))) return rc;
   float* alpha = (float*)(ws + L.alpha);
   float* de = (float*)(ws + L.de);

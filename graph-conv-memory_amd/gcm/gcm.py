@@ -638,6 +638,19 @@ class DenseGCM(torch.nn.Module):
             if m.gather_current(x):
                 cfg.refresh_pointers()
 
+    @staticmethod
+    def _trains_gnn(cfg):
+        """Does any of the six GNN tensors take a gradient?  The live-row chain hangs the observations' gradient on the
+        node of the PARAMETER gradient (RowsChainNode / DxGateNode in csrc/torch_ext/step_ext.cpp, made only when the
+        packed vector requires one): a frozen GNN behind a trainable encoder has no such node, and its beliefs would
+        come back without a grad_fn.  Those calls take the fused per-step node, which differentiates w.r.t. whichever
+        of (x, nodes, parameters) asks.  Looked at only when the observations need a gradient."""
+        for lin in cfg.lins:
+            for p in lin._parameters.values():
+                if p is not None and p.requires_grad:
+                    return True
+        return False
+
     def _forward_rows(self, x, hidden, cfg, flags, link, need_dx=0):
         """The live-row step (csrc/rows_step.hip), checked entry: one kernel forward, no kernel and no
         autograd node per step backward (every step of a chain hangs its belief tensor on one node,
@@ -1071,7 +1084,7 @@ class DenseGCM(torch.nn.Module):
             no_dx = not (torch.is_grad_enabled() and (x.requires_grad or nodes.requires_grad))
             if cfg.sharded:
                 self._gather_sharded(cfg, x)
-            if cfg.rows_ok and (no_dx or (cfg.dx_ok and self.rows_dx)):
+            if cfg.rows_ok and (no_dx or (cfg.dx_ok and self.rows_dx and self._trains_gnn(cfg))):
                 return self._forward_rows(x, hidden, cfg, link[3], link, 0 if no_dx else (2 if self.rows_dx == "steps" else 1))
             if cfg.learned_sel is None and cfg.fold is None:
                 return self._forward_fused(x, nodes, adj, weights, num_nodes, cfg, link[3], link)
@@ -1101,7 +1114,7 @@ class DenseGCM(torch.nn.Module):
             no_dx = not (torch.is_grad_enabled() and (x.requires_grad or nodes.requires_grad))
             if plan.sharded:
                 self._gather_sharded(plan, x)
-            if plan.rows_ok and (no_dx or (plan.dx_ok and self.rows_dx)):
+            if plan.rows_ok and (no_dx or (plan.dx_ok and self.rows_dx and self._trains_gnn(plan))):
                 return self._forward_rows(x, hidden, plan, flags, None, 0 if no_dx else (2 if self.rows_dx == "steps" else 1))
             if plan.learned_sel is None and plan.fold is None:
                 return self._forward_fused(x, nodes, adj, weights, num_nodes, plan, flags)

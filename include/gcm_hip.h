@@ -415,7 +415,7 @@ int gcm_csr_gatconv_fwd(const float* x, const int64_t* row_ptr, const int64_t* c
                         gcm_stream_t stream);
 
 /* Backward.  col_ptr/rows/perm: the CSC by source as for gcm_csr_graphconv_bwd (may be NULL when
- * E == 0).  Outputs (NULL to skip) as the dense backward's. */
+ * E == 0, or when g_bias is the only output asked for).  Outputs (NULL to skip) as the dense backward's. */
 size_t gcm_csr_gatconv_bwd_workspace_bytes(int64_t M, int64_t E, int Fi, int H, int C, int concat);
 int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_ptr, const int64_t* col,
                         const int64_t* col_ptr, const int64_t* rows, const int64_t* perm, const float* w,

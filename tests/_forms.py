@@ -196,10 +196,11 @@ def _selector(inp, dtype, net, step):
     return tr._WatchedLearnedEdge(net, num_edge_samples=kind[1], noise_fn=nf)
 
 
-def _rollout(inp, dtype, form=None, drop_root_bp=False, grad=False):
+def _rollout(inp, dtype, form=None, drop_root_bp=False, grad=False, obs_grad=False):
     """The oracle's per-step loop from hidden = None.  -> namespace: out [T, B, H2], hidden, pre ({layer: the outputs of
     a conv that a ReLU follows, live rows of every step, flat}), adjs, margin / gap of the selector's decisions, and
-    with grad (loss = sum(out * w)) grads {name: gradient} (edge network under "net.")."""
+    with grad (loss = sum(out * w)) grads {name: gradient} (edge network under "net."; obs_grad: the observations'
+    under "obs")."""
     c = CASES[inp.case]
     B, N, F, H1, H2, T = c["shape"]
     gnn, pre, net = _modules(inp, form, dtype)
@@ -218,10 +219,11 @@ def _rollout(inp, dtype, form=None, drop_root_bp=False, grad=False):
     sel = _selector(inp, dtype, net, step)
     r = types.SimpleNamespace(adjs=[], margin=math.inf, gap=math.inf)
     hidden, outs = None, []
+    obs = inp.obs.to(dtype, copy=True).requires_grad_(bool(grad and obs_grad))
     with torch.set_grad_enabled(grad):
         for t in range(T):
             step["t"] = t
-            mx, hidden = od.dense_step(inp.obs[t].to(dtype), hidden, gnn, graph_size=N, edge_selectors=sel,
+            mx, hidden = od.dense_step(obs[t], hidden, gnn, graph_size=N, edge_selectors=sel,
                                        preprocessor=pre)
             outs.append(mx)
             r.adjs.append(hidden[1].detach() != 0)
@@ -231,6 +233,8 @@ def _rollout(inp, dtype, form=None, drop_root_bp=False, grad=False):
             r.grads = {k: p.grad for k, p in gnn.named_parameters()}
             if net is not None:
                 r.grads.update({"net." + k: p.grad for k, p in net.named_parameters()})
+            if obs_grad:
+                r.grads["obs"] = obs.grad
     for h in handles:
         h.remove()
     r.out, r.hidden = out.detach(), tuple(h.detach() for h in hidden)
@@ -261,12 +265,13 @@ def wrong_forms(form, fold=False):
     return out
 
 
-def preconditions(case, form, seed, inp=None, grad=False):
+def preconditions(case, form, seed, inp=None, grad=False, obs_grad=False):
     """What must hold of the oracle's own runs for a comparison under `seed` to mean something (module docstring).
     -> namespace: n_pre, relu_ratio (inf without a ReLU), signs_equal, belief_atol, sens {wrong form: distance / atol},
     margin (euclid), gap / same_edges (learned), r32 / r64 (the two runs; grad: with their gradients)."""
     inp = inp or inputs(case, form, seed)
-    r32, r64 = _rollout(inp, torch.float32, grad=grad), _rollout(inp, torch.float64, grad=grad)
+    r32 = _rollout(inp, torch.float32, grad=grad, obs_grad=obs_grad)
+    r64 = _rollout(inp, torch.float64, grad=grad, obs_grad=obs_grad)
     p = types.SimpleNamespace(case=case, form=form, seed=seed, n_pre=0, relu_ratio=math.inf, signs_equal=True)
     for i, v64 in r64.pre.items():
         v32 = r32.pre[i].double()
@@ -310,24 +315,27 @@ def assert_preconditions(p):
 _cache = {}
 
 
-def trajectory(case, form):
+def trajectory(case, form, obs_grad=None):
     """The oracle's trajectory of (case, form) under its seed, once per process: inputs, preconditions (`pre`), the
     float32 state (`hidden`: nodes, adj, weights, count), the float64 beliefs with their atol, and `bounds`
     {parameter name (| "obs"): (float64 gradient, atol)} - names as the product's modules have them ("pre." / "net."
-    for the preprocessor / edge network)."""
-    key = (case, form)
+    for the preprocessor / edge network).  obs_grad (default: what the case says): the observations take a gradient,
+    so `bounds` has the "obs" entry."""
+    c = CASES[case]
+    obs_grad = bool(c.get("obs_grad")) if obs_grad is None else bool(obs_grad)
+    key = (case, form, obs_grad)
     if key in _cache:
         return _cache[key]
-    c = CASES[case]
     B, N, F, H1, H2, T = c["shape"]
     seed = SEEDS[(case, form_id(form))]
     inp = inputs(case, form, seed)
     t = types.SimpleNamespace(case=case, form=form, seed=seed, inp=inp, shape=c["shape"],
-                              pre=preconditions(case, form, seed, inp, grad=c["sel"][0] == "learned"))
+                              pre=preconditions(case, form, seed, inp, grad=c["sel"][0] == "learned",
+                                                obs_grad=obs_grad))
     if c["sel"][0] != "learned":
         gnn, pre, _ = _modules(inp)
         ref = gnn if pre is None else PreGnn(pre, gnn)
-        obs = inp.obs.clone().requires_grad_(bool(c.get("obs_grad")))
+        obs = inp.obs.clone().requires_grad_(obs_grad)
         watched = []
 
         def factory():
