@@ -38,6 +38,13 @@
 #include "gcm_common.h"
 #include "rows_common.h"
 
+#ifdef GCM_STAMPS   // diagnostic build only (make stamps12, tools/kstamp_bptt_hops.py): STAMP(n) = workgroup 0, wave 0
+__device__ unsigned long long g_stamps[32];
+extern "C" int gcm_debug_read_stamps(unsigned long long* out, int n) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * n);
+}
+#endif
+
 namespace gcm_rows {
 
 struct HopsTable {
@@ -60,6 +67,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
   float* sD2 = sMem;                                      // [NMAX][DS]
   float* sU = sD2 + NMAX * DS;                            // [NMAX][US]  dAgg2 | dH1c
   int* sMap = reinterpret_cast<int*>(sU + NMAX * US);     // [NMAX]      row -> step, -1: none
+  STAMP(0);
 
   // ---- stage: every load of this wave, issued before the first wait ---------------------------------------------------
   const int oq = q < H2 ? q : H2 - 1;
@@ -112,6 +120,11 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
   int mapv = 0xff;
   if (tid < NMAX) mapv = ht.row2step[tid];
   asm volatile("" ::: "memory");
+  STAMP(1);   // every load issued
+#ifdef GCM_STAMPS_WAIT   // (the stamps build's second form: the round trip alone, nothing computed under it)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  STAMP(8);
+#endif
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) w2[kk] = 2 * kk + half < H2 ? w2[kk] : 0.f;
   if (tid < NMAX) sMap[tid] = (mapv < T) ? mapv : -1;
@@ -132,6 +145,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
     aT2 = __builtin_amdgcn_mfma_f32_32x32x2f32(d2, on ? vb[i] : 0.f, aT2, 0, 0, 0);   // d2 (x) h1cur
   }
   __syncthreads();
+  STAMP(2);   // D2, dW2 / db2 partials; barrier
 
   // ---- U = D2 . [W_rel2 | W_root2]: one 32 x 32 tile per wave (rows of steps >= T are never read: skipped) -----------
   if (32 * sb < T) {
@@ -145,6 +159,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
     for (int r = 0; r < 16; ++r) sU[(32 * sb + gcm_fused::acc_row(r, half)) * US + 32 * ch + q] = aU[r];
   }
   __syncthreads();
+  STAMP(3);   // U; barrier
 
   // ---- G1 of the wave's rows: the gather (ascending hop, then the own step), then dW1 / db1 partials -----------------
   f32x16 aR, aT;   // dW_rel1 [h][f], dW_root1 [h][f]
@@ -180,6 +195,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
     aT = __builtin_amdgcn_mfma_f32_32x32x2f32(g1, written ? xr[i] : 0.f, aT, 0, 0, 0);
   }
   __syncthreads();   // (D2 / U / the map are dead: the partial slabs take their place)
+  STAMP(4);   // gather, G1, dW1 / db1 partials; barrier
 
   // ---- one slab per graph: dW_rel1 [H1*F] | dW_root1 [H1*F] | db1 [H1] | dW_rel2 [H2*H1] | dW_root2 [H2*H1] | db2 [H2] ----
   const int Pg = 2 * H1 * F + H1 + 2 * H2 * H1 + H2;
@@ -201,6 +217,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
     if (lane < H2) mine[m_b2 + lane] = s2;
   }
   __syncthreads();
+  STAMP(5);   // the eight partial slabs in LDS; barrier
   float* slab = slabs + (size_t)b * Pg;
   for (int e = tid; e < Pg; e += 512) {
     float t_ = 0.f;
@@ -208,6 +225,7 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
     for (int w = 0; w < NW; ++w) t_ += sMem[(size_t)w * Pg + e];
     slab[e] = t_;
   }
+  STAMP(6);   // summed in wave order, the graph's slab stored
 }
 
 }  // namespace gcm_rows

@@ -669,6 +669,9 @@ struct RowsFast {
   bool col_ok = false;
   int64_t cached_steps = 0, chain_steps = 0, rolled_steps = 0, col_steps = 0;
   at::Tensor cH, cA, cX, wimg, abits;
+  // the weight image the fused head launch (pack_params_head) made beside a packed vector, and that vector: taken by
+  // the chain's first cached step iff it is armed with that very tensor
+  at::Tensor head_img, head_img_of;
   at::Tensor kA, kR;   // the column-write chain's caches: agg1 [B,N,F], root [B,N,H1]
   at::Tensor rH, rA, rX;   // the ring caches of the steady-state steps (copies: the first N records keep reading cH / cA / cX)
   std::shared_ptr<DxChain> dxc;
@@ -981,11 +984,18 @@ struct RowsFast {
       cA = at::empty({B, N, F}, obs.options());
       cX = at::empty({B, N, F}, obs.options());
       if (node) { node->cH = cH; node->cA = cA; node->cX = cX; node->descs = cfg->descs; }
-      // the weights lane-major, once per chain (the parameters are fixed inside one)
-      wimg = at::empty({(int64_t)gcm_dense_rows_cached_weight_image_floats()}, obs.options());
-      check(gcm_dense_rows_cached_weight_image(packed.data_ptr<float>(), wimg.data_ptr<float>(), F, H1, H2,
-                                               reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(dev).stream())),
-            "gcm_dense_rows_cached_weight_image");
+      // the weights lane-major, once per chain (the parameters are fixed inside one): the image that came with this
+      // very packed vector out of the head's one launch, or a launch of its own
+      if (head_img.defined() && head_img_of.unsafeGetTensorImpl() == packed.unsafeGetTensorImpl() &&
+          head_img.numel() == (int64_t)gcm_dense_rows_cached_weight_image_floats()) {
+        wimg = head_img;
+      } else {
+        wimg = at::empty({(int64_t)gcm_dense_rows_cached_weight_image_floats()}, obs.options());
+        check(gcm_dense_rows_cached_weight_image(packed.data_ptr<float>(), wimg.data_ptr<float>(), F, H1, H2,
+                                                 reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(dev).stream())),
+              "gcm_dense_rows_cached_weight_image");
+      }
+      head_img = head_img_of = at::Tensor();
     }
 #ifdef GCM_HOST_PROF
     double prof_t = prof_now();
@@ -1244,6 +1254,11 @@ struct RowsFast {
     dx_gate.reset();
     dx_last.reset();
     packed = at::Tensor();
+    head_img = head_img_of = at::Tensor();
+  }
+  void set_head_image(const at::Tensor& packed_, const at::Tensor& image) {
+    head_img_of = packed_;
+    head_img = image;
   }
 };
 
@@ -1660,16 +1675,8 @@ struct PackNode : public torch::autograd::Node {
   }
 };
 
-at::Tensor pack_params(const std::vector<at::Tensor>& ts) {
-  TORCH_CHECK(!ts.empty());
-  at::Tensor packed;
-  {
-    at::NoGradGuard ng;
-    std::vector<at::Tensor> flat;
-    flat.reserve(ts.size());
-    for (const auto& t : ts) flat.push_back(t.reshape({-1}));
-    packed = at::cat(flat);
-  }
+// `packed` (built without history) as the output of a PackNode over `ts`, when any of them takes a gradient
+static void hang_pack_node(at::Tensor& packed, const std::vector<at::Tensor>& ts) {
   bool any = false;
   for (const auto& t : ts) any = any || t.requires_grad();
   if (at::GradMode::is_enabled() && any) {
@@ -1684,7 +1691,62 @@ at::Tensor pack_params(const std::vector<at::Tensor>& ts) {
     node->set_next_edges(torch::autograd::collect_next_edges(ts));
     torch::autograd::create_gradient_edge(packed, node);   // (adds the input metadata itself)
   }
+}
+
+at::Tensor pack_params(const std::vector<at::Tensor>& ts) {
+  TORCH_CHECK(!ts.empty());
+  at::Tensor packed;
+  {
+    at::NoGradGuard ng;
+    std::vector<at::Tensor> flat;
+    flat.reserve(ts.size());
+    for (const auto& t : ts) flat.push_back(t.reshape({-1}));
+    packed = at::cat(flat);
+  }
+  hang_pack_node(packed, ts);
   return packed;
+}
+
+// pack_params, the cached step's weight image and the zero state of forward(x, None) as ONE launch
+// (gcm_dense_rows_head_fused): -> (packed, image | None, nodes | None, adj | None, num_nodes | None).  want_image: the
+// first six tensors are the GNN's (F, H1, H2 <= 64).  B > 0: the state DenseGCM._fresh_state carves - one allocation,
+// nodes [B,N,feats] | adj [B,N,N] | num_nodes [B] (int64) at 64-float paddings, independent tensors (own version
+// counters, no view relation).  The caller has checked: contiguous fp32 tensors on the current HIP device.
+pybind11::tuple pack_params_head(const std::vector<at::Tensor>& ts, int F, int H1, int H2, bool want_image, int64_t B,
+                                 int64_t N, int64_t feats) {
+  TORCH_CHECK(!ts.empty() && ts.size() <= 16, "pack_params_head: 1 .. 16 tensors");
+  const at::Tensor& t0 = ts[0];
+  std::vector<const float*> srcs;
+  std::vector<size_t> lens;
+  int64_t total = 0;
+  for (const auto& t : ts) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.get_device() == t0.get_device(),
+                "pack_params_head: contiguous float32 tensors on one HIP device");
+    srcs.push_back(t.numel() ? t.data_ptr<float>() : nullptr);
+    lens.push_back((size_t)t.numel());
+    total += t.numel();
+  }
+  TORCH_CHECK(t0.get_device() == c10::hip::current_device(), "pack_params_head: tensors must live on the current device");
+  const auto opts = t0.options().requires_grad(false);
+  at::Tensor packed = at::empty({total}, opts), image, state, nodes, adj, count;
+  if (want_image) image = at::empty({(int64_t)gcm_dense_rows_cached_weight_image_floats()}, opts);
+  int64_t state_floats = 0;
+  if (B > 0) {
+    const int64_t n_nodes = pad64(B * N * feats), n_adj = pad64(B * N * N);
+    state_floats = n_nodes + n_adj + 2 * B;
+    state = at::empty({state_floats}, opts);
+    nodes = alias_of(state, 0, {B, N, feats}, state.dtype());
+    adj = alias_of(state, n_nodes, {B, N, N}, state.dtype());
+    count = alias_of(state, (n_nodes + n_adj) / 2, {B}, caffe2::TypeMeta::Make<int64_t>());
+  }
+  check(gcm_dense_rows_head_fused(srcs.data(), lens.data(), (int)ts.size(), packed.data_ptr<float>(),
+                                  want_image ? image.data_ptr<float>() : nullptr, F, H1, H2,
+                                  B > 0 ? state.data_ptr() : nullptr, sizeof(float) * (size_t)state_floats,
+                                  reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(t0.get_device()).stream())),
+        "gcm_dense_rows_head_fused");
+  hang_pack_node(packed, ts);
+  auto opt = [](const at::Tensor& t) { return t.defined() ? pybind11::cast(t) : pybind11::object(pybind11::none()); };
+  return pybind11::make_tuple(packed, opt(image), opt(nodes), opt(adj), opt(count));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2813,6 +2875,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("donates", [](RowsFast& f) { return f.donate; })
       .def("pending", &RowsFast::pending)
       .def("forget", &RowsFast::forget)
+      .def("set_head_image", &RowsFast::set_head_image)
       .def("steps", [](RowsFast& f) { return f.n_steps; })
       .def("cached_steps", [](RowsFast& f) { return f.cached_steps - f.col_steps; })
       .def("rolled_steps", [](RowsFast& f) { return f.rolled_steps; })
@@ -2832,6 +2895,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("steps", &LearnedChain::steps);
   m.def("learned_step2", &learned_step2);
   m.def("pack_params", &pack_params);
+  m.def("pack_params_head", &pack_params_head);
   pybind11::class_<LearnedFast>(m, "LearnedFast")
       .def(pybind11::init<const std::vector<std::pair<pybind11::object, pybind11::object>>&,
                           const std::vector<pybind11::object>&, pybind11::object>())

@@ -173,6 +173,13 @@ class DenseGCM(torch.nn.Module):
         # the records' live lists not read).  False (env GCM_BPTT_HOPS=0): k_bptt_cached_graph, which every other chain
         # keeps (A/B); read when a chain is armed / a rollout starts
         self.rows_hops_bptt = os.environ.get("GCM_BPTT_HOPS", "1") == "1"
+        # True: the head of a chain - the packed parameter vector, the cached step's weight image and, from hidden = None,
+        # the zero state - is ONE launch (csrc/head_fused.hip) instead of a fill, a cat and the image kernel one behind the
+        # other in front of step 0.  Taken when the six GNN tensors (and the edge network's) are all present, contiguous
+        # fp32 on the current HIP device, and nothing is folded into the vector.  False (env GCM_FUSED_HEAD=0): the three
+        # launches (A/B); the same bits either way
+        self.rows_fused_head = os.environ.get("GCM_FUSED_HEAD", "1") == "1"
+        self._head_ready = None   # (cfg, grad mode) of the packed vector forward(x, None) has just built with the state
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
         self.rollout_time_parallel = True
@@ -530,7 +537,32 @@ class DenseGCM(torch.nn.Module):
         cfg.dx_ok = False      # (a gradient w.r.t. the observations through a folded transform: the layered path)
         return cfg
 
-    def _packed_params(self, cfg, head=False):
+    def _fused_head(self, x):
+        """forward(x, None) with rows_fused_head: the zero state _fresh_state(x) makes AND the packed vector (+ weight
+        image) of this call's configuration out of one launch, or None when the call is not eligible (then _fresh_state
+        and _packed_params run as they always did).  The vector lands in _packed_cache; the _packed_params(head=True)
+        of this very call finds it there (_head_ready)."""
+        if (not self.rows_fused_head or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32 or self.edge_weights
+                or x.device.index != torch.cuda.current_device()):
+            return None
+        N, F = self.graph_size, x.shape[1]
+        last = self._cfg_last
+        if last is not None and last[0] == N and last[1] == F and last[2] == x.device:
+            cfg = last[3]
+        else:   # (what forward() asks below, of tensors that only carry the shape)
+            shape = torch.empty(0, N, F, device=x.device)
+            cfg = self._fused_plan(shape, shape, torch.empty(0, device=x.device), F)
+            if cfg is None:
+                return None
+        state = []
+        self._packed_params(cfg, head=True, fresh=(x.shape[0], N, F, state))
+        self._head_ready = (cfg, torch.is_grad_enabled())
+        if not state or state[0] is None:   # (no one-launch form, or an empty batch: the vector is kept for this call)
+            return None
+        nodes, adj, num_nodes = state
+        return nodes, adj, torch.zeros(0, device=x.device), num_nodes
+
+    def _packed_params(self, cfg, head=False, fresh=None):
         """The six GNN tensors as one flat vector (layout of include/gcm_hip.h "packed parameter
         vector"), so that a step returns ONE gradient tensor.  Rebuilt at the head of every chain
         of hidden states (`head`: hidden is None or not produced by this module - the reference
@@ -550,6 +582,10 @@ class DenseGCM(torch.nn.Module):
         if fold is not None and fold[0] is not None:
             tensors = tensors + (fold[0]._parameters["weight"], fold[0]._parameters["bias"])
         cache = self._packed_cache
+        ready, self._head_ready = self._head_ready, None
+        if (ready is not None and head and cache is not None and ready[0] is cfg
+                and ready[1] == torch.is_grad_enabled() == cache[0]):
+            return cache[1]      # (this call's own head: _fused_head built it with the state a moment ago)
         if cache is not None and not head and not cache[2][0] and cache[0] == torch.is_grad_enabled():
             # valid while the very same tensor objects have not been written to (optimizer steps
             # bump _version; re-assigned Parameters are new objects)
@@ -575,9 +611,21 @@ class DenseGCM(torch.nn.Module):
             Fe = cfg.F
             sizes = sizes + (2 * Fe * Fe, Fe, Fe, Fe, Fe * Fe, Fe, Fe, Fe, Fe, 1)
         dev = tensors[0].device
+        image = None
         if fold is None and all(t is not None for t in tensors):
             # (one autograd node: every parameter's gradient a view)
-            packed = _ops._ext.module().pack_params(list(tensors))
+            if (head and self.rows_fused_head and len(tensors) <= 16 and dev.type == "cuda"
+                    and dev.index == torch.cuda.current_device()
+                    and all(t.dtype is torch.float32 and t.device == dev and t.is_contiguous() for t in tensors)):
+                # ... and the weight image, and a fresh state, out of the same launch
+                want_image = cfg.learned_sel is None and max(cfg.F, cfg.H1, cfg.H2) <= 64
+                B, N, F = fresh[:3] if fresh is not None else (0, 0, 0)
+                packed, image, *state = _ops._ext.module().pack_params_head(
+                    list(tensors), cfg.F, cfg.H1, cfg.H2, want_image, B, N, F)
+                if fresh is not None:
+                    fresh[3].extend(state)
+            else:
+                packed = _ops._ext.module().pack_params(list(tensors))
         else:
             parts = [t.reshape(-1) if t is not None else torch.zeros(n, device=dev)
                      for t, n in zip(tensors, sizes)]
@@ -596,7 +644,7 @@ class DenseGCM(torch.nn.Module):
                 cfg.refresh_pointers()
                 break
         self._packed_cache = (key, packed, used,
-                              [(t, t._version if t is not None else 0) for t in tensors], gate)
+                              [(t, t._version if t is not None else 0) for t in tensors], gate, image)
         return packed
 
     def _gate(self):
@@ -689,6 +737,9 @@ class DenseGCM(torch.nn.Module):
                     | (0 if self.rows_lean_step else _hip.STEP_NOT_LEAN))
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
                 cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
+            image = self._packed_cache[5]
+            if image is not None and self._packed_cache[1] is root:
+                fast.set_head_image(root, image)   # (the first cached step takes it iff it is armed with this vector)
         mx, n2, a2, c2, donate = fast.run(x, nodes, adj, weights, num_nodes, root, flags, cfg.cpp_handle(),
                                           self.donate_state, need_dx, bool(fresh and self.rows_cached_steps))
         if donate:
@@ -1053,7 +1104,7 @@ class DenseGCM(torch.nn.Module):
         parameter vector and the C++ host path are runtime caches (rebuilt on the first call)."""
         d = dict(self.__dict__)
         d.update(_plan_cache=None, _fold=None, _noise_pool=None, _token=object(), _cfg_cache={}, _cfg_last=None,
-                 _packed_cache=None, _flags={}, _pending=[], _pinned_pool=[], _ctr=[0], _fast=None,
+                 _packed_cache=None, _head_ready=None, _flags={}, _pending=[], _pinned_pool=[], _ctr=[0], _fast=None,
                  _learned_chain=None, _flag_user_list=None)
         return d
 
@@ -1065,15 +1116,23 @@ class DenseGCM(torch.nn.Module):
         """x [B, feat]; hidden = (nodes [B,N,feat], adj [B,N,N], weights [B,N,N] | [0],
         num_nodes [B]) or None.  Returns (belief [B, H], new hidden)."""
         if hidden is None:
-            hidden = self._fresh_state(x)
+            hidden = self._fused_head(x) or self._fresh_state(x)
             hidden[0]._gcm_fresh = True     # empty graphs: what the cached LearnedEdge steps may rely on
+            try:
+                return self._forward(x, hidden)
+            finally:
+                self._head_ready = None     # (a head vector no path of this call asked for is not the next call's)
+        return self._forward(x, hidden)
+
+    def _forward(self, x, hidden):
+        """forward() on a hidden state that exists."""
         nodes, adj, weights, num_nodes = hidden
 
         # the kernels are launched on the CURRENT device's stream: tensors on another GPU get a
         # device guard for the call (PyTorch ops in the reference guard implicitly)
         if x.is_cuda and x.device.index != torch.cuda.current_device():
             with torch.cuda.device(x.device):
-                return self.forward(x, hidden)
+                return self._forward(x, hidden)
 
         # A hidden state this module returned itself (same node / adjacency tensors, same input
         # shape): everything checked below held for it by construction.

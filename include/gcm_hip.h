@@ -785,6 +785,9 @@ int gcm_dense_rows_cached_layout(int B, int N, int F, int H1, int H2, size_t* ou
 size_t gcm_dense_rows_cached_weight_image_floats(void);   /* the floats `image` must hold (36864) */
 int gcm_dense_rows_cached_weight_image(const float* params, float* image, int F, int H1, int H2,
                                        gcm_stream_t stream);
+/* The head of a rollout as ONE launch - packed parameter vector, weight image, zero state (csrc/head_fused.hip).
+ * Declared in gcm_hip_head.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_head.h"
 int gcm_dense_rows_step_cached(const float* obs, float* nodes, float* adj, int64_t* count,
                                const gcm_selector_desc* selectors, int n_selectors, const float* params,
                                const float* weight_image, int has_bias, int act1, int act2, float* cache_h1, float* cache_agg1,
