@@ -10,6 +10,7 @@
 // The distance matrix never leaves the chip unless dist_out is given.
 #include "fused_common.h"
 #include "euclid_chain.h"
+#include "dist_view.h"   // View, view_cur, view_cur_row, view_emit (shared with knn.hip)
 
 #ifdef GCM_STAMPS   // diagnostic build only (make stamps6, tools/kstamp_euclid.py)
 __device__ unsigned long long g_stamps[32];
@@ -22,50 +23,6 @@ extern "C" int gcm_debug_read_stamps(unsigned long long* out, int n) {
 #endif
 
 namespace {
-
-// Where a kernel finds the graph.  Either the ADVANCED state (count == nullptr): cur_idx[b] is the row
-// that holds the current node.  Or the state BEFORE the step (count = num_nodes going in, obs = the
-// new nodes): the current node is obs[b], it will land in row cur = min(count, N-1), and after the
-// overflow roll (count + 1 > N) image row j is stored row j + 1.  Same arithmetic either way: the
-// second form lets the live-row step (rows_step.hip) run the distance selectors ahead of its own
-// state advance, with the decisions handed over as a row [B, N] instead of adjacency writes.
-//
-// cur_rows != nullptr: the "current nodes" the distances are taken against come from outside - n_cur rows
-// [n_cur, F], the all-gathered current nodes of EVERY rank of a batch-sharded run (EuclideanEdge's
-// mean runs over all graphs b' of the GLOBAL batch, distance.py:48-49) - instead of the B local ones.
-struct View {
-  const float* nodes;
-  const int64_t* cur_idx;
-  const int64_t* count;
-  const float* obs;
-  const float* cur_rows;
-  int n_cur;
-};
-__device__ __forceinline__ int view_cur(const View& v, int b, int N, int& sh) {
-  sh = 0;
-  int64_t c;
-  if (v.count) {
-    const int64_t n = v.count[b];
-    sh = n + 1 > N ? 1 : 0;
-    c = sh ? n - 1 : n;
-  } else {
-    c = v.cur_idx[b];
-  }
-  return (int)(c < 0 ? 0 : (c > N - 1 ? N - 1 : c));
-}
-__device__ __forceinline__ const float* view_cur_row(const View& v, int b, int cur, int N, int F) {
-  return v.count ? v.obs + (size_t)b * F : v.nodes + ((size_t)b * N + cur) * F;
-}
-// decision for image row j: adjacency entry (advanced state) or the row handed to the step kernel
-__device__ __forceinline__ void view_emit(float* adj, float* sel_row, int b, int cur, int j, int N,
-                                          bool hit, int bidirectional) {
-  if (sel_row) {
-    sel_row[(size_t)b * N + j] = hit ? 1.f : 0.f;
-  } else if (hit) {
-    adj[((size_t)b * N + cur) * N + j] = 1.f;
-    if (bidirectional) adj[((size_t)b * N + j) * N + cur] = 1.f;
-  }
-}
 
 // gather cur rows (scaled) into workspace: ws_cur [B, F]
 __global__ void k_gather_cur(View vw, const float* __restrict__ dist_param,
@@ -1118,6 +1075,9 @@ static int run_distance(const View& vw, float* adj, float* sel_row, int mode, fl
                         float* dist_out, void* workspace, size_t workspace_bytes, int B, int N, int F,
                         gcm_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (mode >> GCM_DIST_KNN_SHIFT)   // k bits: the k nearest candidates instead of a threshold (knn.hip)
+    return gcm_knn_run(vw, adj, sel_row, mode, max_distance, dist_param, a0, a1, b0, b1, bidirectional, dist_out, B,
+                       N, F, s);
   if (vw.cur_rows && mode != GCM_DIST_EUCLID_CROSSBATCH) return GCM_EINVAL;   // only the cross-batch mean couples graphs
   if (mode == GCM_DIST_EUCLID_CROSSBATCH) {
     if (F > 128 || B > 65535) return GCM_EUNSUPPORTED;

@@ -52,6 +52,10 @@ WINDOW_PROTOTYPES = _abi.prototypes(_WINDOW_HEADER)
 _CONSTANTS.update(_abi.constants(_WINDOW_HEADER))
 # and the section from gcm_hip_head.h (the head of a rollout as one launch: packed vector, weight image, zero state)
 HEAD_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_head.h"))
+# and the section from gcm_hip_knn.h (KNNEdge: the distance modes that carry k)
+_KNN_HEADER = _abi.header("gcm_hip_knn.h")
+KNN_PROTOTYPES = _abi.prototypes(_KNN_HEADER)
+_CONSTANTS.update(_abi.constants(_KNN_HEADER))
 globals().update({name[4:]: value for name, value in _CONSTANTS.items()})   # GCM_ACT_TANH -> ACT_TANH, ...
 GCM_EUNSUPPORTED = _CONSTANTS["GCM_EUNSUPPORTED"]
 DIR = {d: _CONSTANTS["GCM_DIR_" + d.upper()] for d in ("forward", "backward", "both")}
@@ -99,6 +103,7 @@ def lib():
         bind(handle, PNA_PROTOTYPES)
         bind(handle, WINDOW_PROTOTYPES)
         bind(handle, HEAD_PROTOTYPES)
+        bind(handle, KNN_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

@@ -3,6 +3,8 @@
 
 temporal.TemporalBackedge, dense.DenseEdge            index writes, folded into the step kernels
 distance.EuclideanEdge / CosineEdge / SpatialEdge     fused pairwise distance + threshold kernels
+knn.KNNEdge                                           k nearest stored nodes (L2 on pose slices / cosine):
+                                                      distances, ranks and the adjacency row in one kernel
 learned.LearnedEdge                                   candidate pairs + gumbel-softmax/STE kernels
                                                       around a user-replaceable edge network
 """

@@ -163,6 +163,9 @@ int gcm_edge_distance_ex(const float* nodes, float* adj, const int64_t* cur_idx,
                          int bidirectional, float* dist_out, const float* cur_rows, int n_cur_rows,
                          void* workspace, size_t workspace_bytes, int B, int N, int F,
                          gcm_stream_t stream);
+/* `mode` with k bits (metric | k << GCM_DIST_KNN_SHIFT): the k nearest stored nodes instead of a threshold (KNNEdge).
+ * Declared in gcm_hip_knn.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_knn.h"
 
 /* ---- DenseGraphConv (PyG; call sites README.md:56-62) ---------------------- */
 
