@@ -46,6 +46,8 @@ TAG_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_tag.h"))
 _PNA_HEADER = _abi.header("gcm_hip_pna.h")
 PNA_PROTOTYPES = _abi.prototypes(_PNA_HEADER)
 _CONSTANTS.update(_abi.constants(_PNA_HEADER))
+# and the section from gcm_hip_gen.h (the softmax aggregation of GENConv / DenseGENConv and its gradients)
+GEN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gen.h"))
 # and the section from gcm_hip_window.h (SparseGCM.drop_oldest / reset_hidden / overflow="wrap")
 _WINDOW_HEADER = _abi.header("gcm_hip_window.h")
 WINDOW_PROTOTYPES = _abi.prototypes(_WINDOW_HEADER)
@@ -101,6 +103,7 @@ def lib():
         bind(handle, GATED_PROTOTYPES)
         bind(handle, TAG_PROTOTYPES)
         bind(handle, PNA_PROTOTYPES)
+        bind(handle, GEN_PROTOTYPES)
         bind(handle, WINDOW_PROTOTYPES)
         bind(handle, HEAD_PROTOTYPES)
         bind(handle, KNN_PROTOTYPES)

@@ -1678,6 +1678,94 @@ def csr_pnaconv(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, c
     return _CsrPNAConv.apply(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, cfg)
 
 
+# ---------------------------------------------------------------------------
+# GENConv / DenseGENConv (PyG, aggr="softmax"; csrc/genconv.hip): the softmax aggregation alone - lin_src / lin_dst,
+# the message norm and the mlp stay in torch
+# ---------------------------------------------------------------------------
+def _gen_operands(xs, t):
+    xs, t = xs.contiguous(), t.contiguous()
+    _hip.on_device(xs, t)
+    assert xs.dtype == _f32, "the GEN aggregation is float32 only"
+    assert t.numel() == 1 and t.dtype == _f32
+    return xs, t
+
+
+class _DenseGENAgg(torch.autograd.Function):
+    """agg_ic = sum_j a_ijc m_jc over {j: adj[b,i,j] != 0}, m = relu(xs) + eps, a = softmax_j(t m_jc); xs [B,N,C],
+    adj [B,N,N] (pattern only: no gradient), t [1] (read on the device)."""
+
+    @staticmethod
+    def forward(ctx, xs, adj, t, eps):
+        xs, t = _gen_operands(xs, t)
+        adj = adj.contiguous()
+        _hip.on_device(adj)
+        B, N, C = xs.shape
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        agg = torch.empty(B, N, C, device=xs.device, dtype=_f32)
+        lse = torch.empty(2, B, N, C, device=xs.device, dtype=_f32)
+        bits = torch.empty(B * N, (N + 63) // 64, device=xs.device, dtype=torch.int64)   # the pattern, 1 bit an entry
+        _call("gcm_dense_gen_fwd", _hip.ptr(xs), _hip.ptr(adj), _hip.ptr(t), eps, _hip.ptr(agg), _hip.ptr(lse),
+              _hip.ptr(bits), B, N, C, _hip.stream())
+        ctx.save_for_backward(xs, bits, t, agg, lse)
+        ctx.eps = eps
+        return agg
+
+    @staticmethod
+    def backward(ctx, g_agg):
+        xs, bits, t, agg, lse = ctx.saved_tensors
+        B, N, C = xs.shape
+        need_x, _, need_t, _ = ctx.needs_input_grad
+        g_agg = g_agg.contiguous()
+        g_xs = torch.empty_like(xs) if need_x else None
+        g_t = torch.empty_like(t) if need_t else None
+        ws, ws_bytes = _scratch("gcm_dense_gen_bwd", B, N, C, device=xs.device) if need_t else (None, 0)
+        _call("gcm_dense_gen_bwd", _hip.ptr(g_agg), _hip.ptr(xs), _hip.ptr(bits), _hip.ptr(t), ctx.eps, _hip.ptr(agg),
+              _hip.ptr(lse), _hip.ptr(g_xs), _hip.ptr(g_t), _hip.ptr(ws), ws_bytes, B, N, C, _hip.stream())
+        return g_xs, None, g_t, None
+
+
+def dense_genagg(xs, adj, t, eps=1e-7):
+    return _DenseGENAgg.apply(xs, adj.detach(), t, float(eps))
+
+
+class _CsrGENAgg(torch.autograd.Function):
+    """The same aggregation over the in-edges of every node of `graph` (every CSR entry is one term); xs [M,C]."""
+
+    @staticmethod
+    def forward(ctx, xs, t, graph, eps):
+        xs, t = _gen_operands(xs, t)
+        M, C = xs.shape
+        assert M == graph.M
+        agg = torch.empty(M, C, device=xs.device, dtype=_f32)
+        lse = torch.empty(2, M, C, device=xs.device, dtype=_f32)
+        _call("gcm_csr_gen_fwd", _hip.ptr(xs), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(t), eps,
+              _hip.ptr(agg), _hip.ptr(lse), M, graph.E, C, _hip.stream())
+        ctx.save_for_backward(xs, t, agg, lse)
+        ctx.graph, ctx.eps = graph, eps
+        return agg
+
+    @staticmethod
+    def backward(ctx, g_agg):
+        xs, t, agg, lse = ctx.saved_tensors
+        graph = ctx.graph
+        M, C = xs.shape
+        E = graph.E
+        need_x, need_t, _, _ = ctx.needs_input_grad
+        g_agg = g_agg.contiguous()
+        col_ptr, rows, _ = _csc_or_none(graph, need_x and E > 0)
+        g_xs = torch.empty_like(xs) if need_x else None
+        g_t = torch.empty_like(t) if need_t else None
+        ws, ws_bytes = _scratch("gcm_csr_gen_bwd", M, E, C, device=xs.device) if need_t else (None, 0)
+        _call("gcm_csr_gen_bwd", _hip.ptr(g_agg), _hip.ptr(xs), _hip.ptr(t), ctx.eps, _hip.ptr(agg), _hip.ptr(lse),
+              _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(g_xs),
+              _hip.ptr(g_t), _hip.ptr(ws), ws_bytes, M, E, C, _hip.stream())
+        return g_xs, g_t, None, None
+
+
+def csr_genagg(xs, t, graph, eps=1e-7):
+    return _CsrGENAgg.apply(xs, t, graph, float(eps))
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

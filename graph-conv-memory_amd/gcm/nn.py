@@ -1016,6 +1016,166 @@ class PNAConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, towers={self.towers})"
 
 
+class _SoftmaxAggr(torch.nn.Module):
+    """Holder of GENConv's temperature under PyG's key `aggr_module.t` [1]: a Parameter when learnt, else a
+    persistent buffer."""
+
+    def __init__(self, learn):
+        super().__init__()
+        if learn:
+            self.t = torch.nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("t", torch.empty(1))
+
+
+class _MessageNorm(torch.nn.Module):
+    """PyG's MessageNorm: msg / max(|msg|_2, 1e-12) * |x|_2 * scale; `scale` [1] is trained with learn_scale."""
+
+    def __init__(self, learn_scale):
+        super().__init__()
+        self.scale = torch.nn.Parameter(torch.empty(1), requires_grad=learn_scale)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.scale.data.fill_(1.0)
+
+    def forward(self, x, msg):
+        msg = torch.nn.functional.normalize(msg, p=2.0, dim=-1)
+        return msg * x.norm(p=2, dim=-1, keepdim=True) * self.scale
+
+
+_GEN_NORMS = {"batch": torch.nn.BatchNorm1d, "layer": torch.nn.LayerNorm}
+
+
+def _gen_init(conv, name, in_channels, out_channels, aggr, t, learn_t, p, learn_p, msg_norm, learn_msg_scale, norm,
+              num_layers, expansion, eps, bias, edge_dim):
+    if edge_dim is not None:
+        raise NotImplementedError(f"{name}(edge_dim=...) is not implemented: edge features do not enter the message")
+    if aggr != "softmax":
+        raise NotImplementedError(f"{name}(aggr={aggr!r}) is not implemented: 'softmax' only")
+    if learn_p:
+        raise NotImplementedError(f"{name}(learn_p=True) is not implemented: p belongs to the power mean")
+    if norm == "instance":
+        raise NotImplementedError(f"{name}(norm='instance') is not implemented: 'batch', 'layer' or None")
+    if norm is not None and norm not in _GEN_NORMS:
+        raise ValueError(f"{name}: unknown norm {norm!r}: 'batch', 'layer' or None")
+    if not isinstance(in_channels, int):
+        raise NotImplementedError(f"{name}: a tuple of in_channels (bipartite graphs) is not implemented")
+    conv.in_channels, conv.out_channels, conv.aggr, conv.eps = in_channels, out_channels, aggr, float(eps)
+    conv.initial_t, conv.learn_t, conv.p, conv.norm = float(t), bool(learn_t), p, norm
+    conv.num_layers, conv.expansion = num_layers, expansion
+    if in_channels != out_channels:
+        conv.lin_src = torch.nn.Linear(in_channels, out_channels, bias=bias)
+        conv.lin_dst = torch.nn.Linear(in_channels, out_channels, bias=bias)
+    conv.aggr_module = _SoftmaxAggr(learn_t)
+    if msg_norm:
+        conv.msg_norm = _MessageNorm(learn_msg_scale)
+    channels = [out_channels] + [out_channels * expansion] * (num_layers - 1) + [out_channels]
+    layers = []
+    for i in range(1, len(channels)):
+        layers.append(torch.nn.Linear(channels[i - 1], channels[i], bias=bias))
+        if i < len(channels) - 1:
+            if norm is not None:
+                layers.append(_GEN_NORMS[norm](channels[i]))
+            layers += [torch.nn.ReLU(), torch.nn.Dropout(0.0)]
+    conv.mlp = torch.nn.Sequential(*layers)
+    conv.reset_parameters()
+
+
+def _gen_reset(conv):
+    _gin_reset(conv.mlp)
+    for name in ("lin_src", "lin_dst", "msg_norm"):
+        if hasattr(conv, name):
+            getattr(conv, name).reset_parameters()
+    conv.aggr_module.t.data.fill_(conv.initial_t)
+
+
+def _gen_source(conv, x):
+    """xs, what the aggregation kernels read: lin_src(x), or x itself when the widths agree."""
+    _hip.on_device(x, conv.aggr_module.t)   # a CPU call fails here, before any torch module runs
+    if x.dtype != torch.float32:
+        raise TypeError("x must be float32; got %s" % x.dtype)
+    return conv.lin_src(x) if hasattr(conv, "lin_src") else x
+
+
+def _gen_tail(conv, x, agg):
+    """Message norm, the residual with x_dst and the mlp over the rows [rows, C] (torch modules)."""
+    if hasattr(conv, "msg_norm"):
+        agg = conv.msg_norm(x, agg)
+    out = agg + (conv.lin_dst(x) if hasattr(conv, "lin_dst") else x)
+    return conv.mlp(out.reshape(-1, conv.out_channels)).view(*out.shape[:-1], conv.out_channels)
+
+
+_GEN_DOC = """m = relu(xs) + eps with xs = lin_src(x) (x itself when in_channels == out_channels); per channel c a
+    node i averages the m_jc of its in-neighbours with the weights softmax_j(t m_jc): t = 0 is the mean, t -> inf the
+    max, and every neighbour gets a gradient.  A node without in-edges aggregates 0.  With msg_norm the aggregate is
+    scaled to agg / max(|agg|_2, 1e-12) * |x_i|_2 * scale (x the raw input).  out = mlp(agg + x_dst), x_dst =
+    lin_dst(x) or x.  The aggregation and its gradients (xs, t) are HIP kernels (csrc/genconv.hip): one online-softmax
+    pass per destination row, shifted by the row's own maximum, so logits of any size are exact; t is read on the
+    device, so a layer with learn_t is HIP-graph capturable.  lin_src, lin_dst, the message norm and the mlp are torch
+    modules.  Parameters as PyG 2.x: `lin_src.*` / `lin_dst.*` (only when the widths differ), `aggr_module.t` [1]
+    (Parameter with learn_t, else a buffer), `msg_norm.scale` [1] (only with msg_norm; trained with learn_msg_scale),
+    `mlp.*`: Linear, norm, ReLU, Dropout(0) per hidden layer of width out_channels * expansion, then a Linear
+    (`mlp.0`, `mlp.1`, `mlp.4` with the defaults); `bias` governs every Linear.  norm: "batch" (BatchNorm1d), "layer"
+    (LayerNorm) or None.  float32, out_channels <= 128.  Not implemented (NotImplementedError): edge_dim, any aggr but
+    "softmax" (lists included), learn_p, norm="instance", a tuple of in_channels."""
+
+
+class DenseGENConv(torch.nn.Module):
+    __doc__ = """DeeperGCN's GENConv with softmax aggregation (PyG's GENConv) on a dense adjacency: x [B,N,F] or
+    [N,F], adj [B,N,N], [1,N,N] or [N,N] float32 (adj[b,i,j] != 0: i aggregates from j).  Only the pattern of adj is
+    read, as in the max aggregation: its values do not matter and it gets no gradient; the diagonal is an ordinary
+    entry and no loop is added.  The output is multiplied by the mask.
+    """ + _GEN_DOC + """  The mlp sees the rows as [B * N, C]: norm="batch" takes its statistics over padded rows
+    too - inside a memory use norm="layer" or None.  Loads GENConv's state_dict.  Not a DenseGraphConv: DenseGCM runs
+    a stack of these through its layered path."""
+
+    def __init__(self, in_channels, out_channels, aggr="softmax", t=1.0, learn_t=False, p=1.0, learn_p=False,
+                 msg_norm=False, learn_msg_scale=False, norm="batch", num_layers=2, expansion=2, eps=1e-7, bias=False,
+                 edge_dim=None):
+        super().__init__()
+        _gen_init(self, "DenseGENConv", in_channels, out_channels, aggr, t, learn_t, p, learn_p, msg_norm,
+                  learn_msg_scale, norm, num_layers, expansion, eps, bias, edge_dim)
+
+    def reset_parameters(self):
+        _gen_reset(self)
+
+    def forward(self, x, adj, mask=None):
+        x, adj = _dense_inputs(x, adj)
+        agg = _ops.dense_genagg(_gen_source(self, x), adj, self.aggr_module.t, self.eps)
+        return _masked(_gen_tail(self, x, agg), mask, x)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, aggr={self.aggr})"
+
+
+class GENConv(torch.nn.Module):
+    __doc__ = """DeeperGCN's GENConv with softmax aggregation (PyG's GENConv, flow source_to_target) without edge
+    features: edge_index [2,E] = (source, sink), x [M,F].  The edges are used as given: no loop is added or removed,
+    an i -> i edge is an ordinary term, duplicates count once each; there are no edge weights.  Uses the
+    `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed here.
+    """ + _GEN_DOC + """  Loads DenseGENConv's state_dict.  Not a GraphConv: SparseGCM runs a stack of these through
+    its generic path."""
+
+    def __init__(self, in_channels, out_channels, aggr="softmax", t=1.0, learn_t=False, p=1.0, learn_p=False,
+                 msg_norm=False, learn_msg_scale=False, norm="batch", num_layers=2, expansion=2, eps=1e-7, bias=False,
+                 edge_dim=None):
+        super().__init__()
+        _gen_init(self, "GENConv", in_channels, out_channels, aggr, t, learn_t, p, learn_p, msg_norm,
+                  learn_msg_scale, norm, num_layers, expansion, eps, bias, edge_dim)
+
+    def reset_parameters(self):
+        _gen_reset(self)
+
+    def forward(self, x, edge_index):
+        xs = _gen_source(self, x)
+        graph = _graph_of(x, edge_index, "GENConv")
+        return _gen_tail(self, x, _ops.csr_genagg(xs, self.aggr_module.t, graph, self.eps))
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, aggr={self.aggr})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
