@@ -52,6 +52,10 @@ GEN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gen.h"))
 _WINDOW_HEADER = _abi.header("gcm_hip_window.h")
 WINDOW_PROTOTYPES = _abi.prototypes(_WINDOW_HEADER)
 _CONSTANTS.update(_abi.constants(_WINDOW_HEADER))
+# and the section from gcm_hip_segments.h (SparseGCM.rollout(x, reset=mask): resets inside one call)
+_SEGMENT_HEADER = _abi.header("gcm_hip_segments.h")
+SEGMENT_PROTOTYPES = _abi.prototypes(_SEGMENT_HEADER)
+_CONSTANTS.update(_abi.constants(_SEGMENT_HEADER))
 # and the section from gcm_hip_head.h (the head of a rollout as one launch: packed vector, weight image, zero state)
 HEAD_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_head.h"))
 # and the section from gcm_hip_knn.h (KNNEdge: the distance modes that carry k)
@@ -105,6 +109,7 @@ def lib():
         bind(handle, PNA_PROTOTYPES)
         bind(handle, GEN_PROTOTYPES)
         bind(handle, WINDOW_PROTOTYPES)
+        bind(handle, SEGMENT_PROTOTYPES)
         bind(handle, HEAD_PROTOTYPES)
         bind(handle, KNN_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]

@@ -620,6 +620,154 @@ def sparse_drop_oldest(nodes, idx, values, T, k):
     return nodes_out, idx_out, values_out, T_out, bptr
 
 
+# ---------------------------------------------------------------------------
+# Episode resets inside one SparseGCM call: the segment layout (include/gcm_hip_segments.h)
+# ---------------------------------------------------------------------------
+class SegmentPlan:
+    """gcm_sparse_seg_plan over (mask u8 [B,t], taus [B], T [B], the stored list idx [3,E] or None) and its ONE
+    readback: Bp virtual graphs, tp columns, n_resets valid resets, E_keep stored edges that stay.  vbase [B+1],
+    table [SEG_ROWS, cap], relabel [B], chunk_off: what the movement kernels below take."""
+
+    def __init__(self, mask, taus, T, idx):
+        mask, taus, T = mask.contiguous(), taus.contiguous(), T.contiguous()
+        idx = None if idx is None or idx.shape[1] == 0 else idx.contiguous()
+        _hip.on_device(mask, taus, T, idx)
+        self.B, self.t = mask.shape
+        self.E = 0 if idx is None else idx.shape[1]
+        B, t, dev = self.B, self.t, mask.device
+        self.cap = B * (t + 1)
+        self.vbase = torch.empty(B + 1, dtype=_i64, device=dev)
+        self.table = torch.empty(_hip.SPARSE_SEG_ROWS, self.cap, dtype=_i64, device=dev)
+        self.relabel = torch.empty(B, dtype=_i64, device=dev)
+        self.chunk_off = torch.empty(-(-self.E // _hip.SPARSE_SEG_CHUNK) + 1, dtype=_i64, device=dev)
+        totals = torch.empty(_hip.SPARSE_SEG_TOTALS, dtype=_i64, device=dev)
+        _call("gcm_sparse_seg_plan", _hip.ptr(mask), _hip.ptr(taus), _hip.ptr(T), _hip.ptr(idx), _hip.ptr(self.vbase),
+              _hip.ptr(self.table), self.cap, _hip.ptr(self.relabel), _hip.ptr(self.chunk_off), _hip.ptr(totals),
+              self.E, B, t, _hip.stream())
+        self.Bp, self.tp, self.n_resets, self.E_keep = (int(v) for v in totals.tolist())      # the one readback
+
+    def row(self, which):
+        """Row `which` (a SPARSE_SEG_* constant) of the table, its Bp written entries."""
+        return self.table[which, :self.Bp]
+
+
+class _SegRows(torch.autograd.Function):
+    """Rows between the batch layout [B,t,F] and the segment layout [Bp,tp,F] (gcm_sparse_seg_rows); each direction
+    is the other's adjoint."""
+
+    @staticmethod
+    def forward(ctx, src, plan, to_segments):
+        src = src.contiguous()
+        _hip.on_device(src)
+        p, F = plan, src.shape[-1]
+        want = (p.B, p.t) if to_segments else (p.Bp, p.tp)
+        if tuple(src.shape[:2]) != want:
+            raise ValueError(f"expected rows of shape {list(want)}, got {list(src.shape[:2])}")
+        out = torch.empty((p.Bp, p.tp, F) if to_segments else (p.B, p.t, F), dtype=_f32, device=src.device)
+        if out.numel():
+            _call("gcm_sparse_seg_rows", _hip.ptr(src), _hip.ptr(p.table), p.cap, _hip.ptr(out), p.Bp, p.tp, p.B, p.t,
+                  F, 0 if to_segments else 1, _hip.stream())
+        ctx.plan, ctx.to_segments = plan, to_segments
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegRows.apply(g, ctx.plan, not ctx.to_segments), None, None
+
+
+def seg_rows(src, plan, to_segments):
+    return _SegRows.apply(src, plan, to_segments)
+
+
+class _SegNodes(torch.autograd.Function):
+    """Node matrices between [B,N,F] and [Bp,N,F] (gcm_sparse_seg_nodes): final=False pairs a graph with its first
+    virtual graph unless that one enters empty, final=True with its last one."""
+
+    @staticmethod
+    def forward(ctx, src, plan, final, to_segments):
+        src = src.contiguous()
+        _hip.on_device(src)
+        p = plan
+        _, N, F = src.shape
+        if src.shape[0] != (p.B if to_segments else p.Bp):
+            raise ValueError(f"expected {p.B if to_segments else p.Bp} node matrices, got {src.shape[0]}")
+        out = torch.empty(p.Bp if to_segments else p.B, N, F, dtype=_f32, device=src.device)
+        if out.numel():
+            _call("gcm_sparse_seg_nodes", _hip.ptr(src), _hip.ptr(p.vbase), _hip.ptr(p.table), p.cap, _hip.ptr(out),
+                  p.Bp, p.B, N, F, int(final), int(to_segments), _hip.stream())
+        ctx.plan, ctx.final, ctx.to_segments = plan, final, to_segments
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegNodes.apply(g, ctx.plan, ctx.final, not ctx.to_segments), None, None, None
+
+
+def seg_nodes(src, plan, final, to_segments):
+    return _SegNodes.apply(src, plan, final, to_segments)
+
+
+class _SegEdges(torch.autograd.Function):
+    """The survivors of a coalesced list under a relabelling of its batches (gcm_sparse_seg_edges), order kept:
+    (values [E]; idx [3,E], relabel [B_old], chunk_off, E_new) -> (idx' [3,E_new], values' [E_new])."""
+
+    @staticmethod
+    def forward(ctx, values, idx, relabel, chunk_off, E_new, B_old, B_new):
+        values, idx = values.contiguous(), idx.contiguous()
+        _hip.on_device(values, idx, relabel, chunk_off)
+        E, dev = idx.shape[1], idx.device
+        idx_out = torch.empty(3, E_new, dtype=_i64, device=dev)
+        values_out = torch.empty(E_new, dtype=_f32, device=dev)
+        src_pos = torch.empty(E_new, dtype=_i64, device=dev)
+        if E_new:
+            _call("gcm_sparse_seg_edges", _hip.ptr(idx), _hip.ptr(values), _hip.ptr(relabel), _hip.ptr(chunk_off),
+                  _hip.ptr(idx_out), _hip.ptr(values_out), _hip.ptr(src_pos), E, E_new, B_old, B_new, _hip.stream())
+        ctx.save_for_backward(src_pos)
+        ctx.dims = (E, E_new)
+        ctx.mark_non_differentiable(idx_out)
+        return idx_out, values_out
+
+    @staticmethod
+    def backward(ctx, _g_idx, g_values):
+        (src_pos,) = ctx.saved_tensors
+        E, E_new = ctx.dims
+        if g_values is None:
+            return (None,) * 7
+        g_values = g_values.contiguous()
+        gv = torch.empty(E, dtype=_f32, device=src_pos.device)
+        _call("gcm_sparse_drop_values_bwd", _hip.ptr(g_values) if E_new else None, _hip.ptr(src_pos) if E_new else None,
+              _hip.ptr(gv) if E else None, E, E_new, _hip.stream())
+        return gv, None, None, None, None, None, None
+
+
+def seg_expand_edges(idx, values, plan):
+    """The stored list in the segment layout: batch b -> vbase[b]; the graphs whose column 0 resets lose theirs."""
+    return _SegEdges.apply(values, idx, plan.relabel, plan.chunk_off, plan.E_keep, plan.B, plan.Bp)
+
+
+def seg_collect_edges(idx, values, plan):
+    """The entries of the call's list that belong to the last virtual graph of every b, relabelled to b; one readback
+    (their count)."""
+    idx = idx.contiguous()
+    _hip.on_device(idx)
+    E = idx.shape[1]
+    n_chunks = -(-E // _hip.SPARSE_SEG_CHUNK)
+    chunk_off = torch.empty(n_chunks + 1, dtype=_i64, device=idx.device)
+    final = plan.row(_hip.SPARSE_SEG_FINAL)
+    _call("gcm_sparse_seg_edges_plan", _hip.ptr(idx) if E else None, _hip.ptr(final), _hip.ptr(chunk_off), E, plan.Bp,
+          _hip.stream())
+    E_new = int(chunk_off[n_chunks].item()) if E else 0            # the one readback
+    return _SegEdges.apply(values, idx, final, chunk_off, E_new, plan.Bp, plan.B)
+
+
+def seg_final_T(T_seg, plan):
+    T_seg = T_seg.contiguous()
+    _hip.on_device(T_seg)
+    out = torch.empty(plan.B, dtype=_i64, device=T_seg.device)
+    _call("gcm_sparse_seg_final_T", _hip.ptr(T_seg), _hip.ptr(plan.vbase), _hip.ptr(out), plan.Bp, plan.B, _hip.stream())
+    return out
+
+
 def _scratch(name, *dims, device):
     """(uint8 tensor, nbytes) of the size the library's `<name>_workspace_bytes(*dims)` asks for: a backward's
     workspace or what a forward saves for its backward."""

@@ -229,19 +229,82 @@ class SparseGCM(torch.nn.Module):
             SparseGCM.did_warn = True
         return self._drop(nodes, adj, T, (T + taus - N).clamp_(min=0))[:3]
 
-    def rollout(self, x, hidden=None, taus=None):
+    def rollout(self, x, hidden=None, taus=None, reset=None):
         """The time-batched entry (the shape RLlib's wrapper holds: x [B, T, feat], batch first):
         T memory steps of every graph in ONE call - which is what forward() already is for SparseGCM (the reference's
         own tests pin one call == T single-node calls, tests/test_sparse_gcm.py:395-540): forward(x, taus = T for every
         graph, hidden).  A stepwise caller (x [B, 1, F] per call, ray_sparse_gcm.py:198-213) pays ~50 us of host and
-        launch cost per call; whole episodes through here run at the one-shot rate (bench.py --config cfg4)."""
+        launch cost per call; whole episodes through here run at the one-shot rate (bench.py --config cfg4).
+        reset: bool [B, T] (device or CPU), DenseGCM.rollout's convention - reset[b, s] empties graph b before x[b, s]
+        is inserted; see forward()."""
         if taus is None:
             taus = torch.full((x.shape[0],), x.shape[1], dtype=torch.long, device=x.device)
-        return self(x, taus, hidden)
+        if reset is None:
+            return self(x, taus, hidden)
+        return self(x, taus, hidden, reset=reset)
 
-    def forward(self, x, taus, hidden):
+    def _forward_segments(self, x, taus, hidden, reset):
+        """forward() with episode resets inside the call: graph b with m valid resets (reset[b, s] with
+        s < taus[b]) becomes m + 1 virtual graphs of ONE ordinary call - the first enters with the stored state (empty
+        when column 0 resets), the others empty - so positions, hops, candidates and positional encodings restart at 0
+        in every episode by construction, and only the longest episode has to fit graph_size.  The outputs are
+        scattered back to [B, t, H]; the returned state is every graph's last virtual graph.  Kernels:
+        csrc/sparse_segments.hip; two host reads more than the call without resets (the plan's totals, the returned
+        list's size), one when the mask has no valid entry - then the call runs as it is."""
+        if not isinstance(reset, torch.Tensor) or reset.dtype != torch.bool:
+            raise TypeError("reset must be a torch.bool tensor, got "
+                            f"{reset.dtype if isinstance(reset, torch.Tensor) else type(reset).__name__}")
+        if x.dim() != 3 or tuple(reset.shape) != tuple(x.shape[:2]):
+            raise ValueError(f"reset must have shape {list(x.shape[:2])}, got {list(reset.shape)}")
+        if x.is_cuda and x.device.index != torch.cuda.current_device():
+            with torch.cuda.device(x.device):
+                return self._forward_segments(x, taus, hidden, reset)
+        B, t, _ = x.shape
+        if B == 0 or t == 0:
+            return self.forward(x, taus, hidden)
+        assert x.dtype == torch.float32 and taus.dtype == torch.long
+        if reset.device != x.device:
+            reset = reset.to(x.device)
+        if hidden is None:
+            nodes = adj = None
+            T = torch.zeros(B, dtype=torch.long, device=x.device)
+        else:
+            nodes, adj, T = hidden
+            assert T.dtype == torch.long
+            adj = adj.coalesce()
+        plan = _ops.SegmentPlan(reset.contiguous().view(torch.uint8), taus, T, None if adj is None else adj.indices())
+        if plan.n_resets == 0:
+            return self.forward(x, taus, hidden)
+        self._chain = None           # its caches depend on the nodes a reset removes
+        hs = None
+        if hidden is not None:
+            idx_s, val_s = _ops.seg_expand_edges(adj.indices(), adj.values(), plan)
+            hs = (_ops.seg_nodes(nodes, plan, False, True),
+                  torch.sparse_coo_tensor(idx_s, val_s, size=(plan.Bp,) + tuple(adj.shape[1:]), is_coalesced=True),
+                  plan.row(_hip.SPARSE_SEG_T))
+        stepwise, self.stepwise_cache = self.stepwise_cache, False      # (no chain over virtual graphs)
+        try:
+            out_s, (nodes_s, adj_s, T_s) = self.forward(_ops.seg_rows(x, plan, True), plan.row(_hip.SPARSE_SEG_LEN),
+                                                        hs)
+        finally:
+            self.stepwise_cache = stepwise
+        out = _ops.seg_rows(out_s, plan, False)
+        adj_s = adj_s.coalesce()
+        idx_f, val_f = _ops.seg_collect_edges(adj_s.indices(), adj_s.values(), plan)
+        adj_f = torch.sparse_coo_tensor(idx_f, val_f, size=(B,) + tuple(adj_s.shape[1:]), is_coalesced=True)
+        adj_f.gcm_bptr = _ops.ptr_from_sorted(idx_f[0], B)
+        T_f = _ops.seg_final_T(T_s, plan)
+        if self._full_T is T_s:      # (a wrapped inner call: the next call on this state wraps too)
+            self._full_T = T_f
+        return out, (_ops.seg_nodes(nodes_s, plan, True, False), adj_f, T_f)
+
+    def forward(self, x, taus, hidden, reset=None):
         """x [B, t, feat] zero padded in t; taus [B] valid lengths; hidden (nodes, adj, T) or
-        None.  Returns (mx [B, t, H] zero padded, (nodes, adj, T + taus))."""
+        None.  Returns (mx [B, t, H] zero padded, (nodes, adj, T + taus)).
+        reset: None, or bool [B, t] - reset[b, s] with s < taus[b] empties graph b (zero rows, no edges, T_b = 0)
+        before x[b, s] is inserted; entries in the padding are ignored (_forward_segments)."""
+        if reset is not None:
+            return self._forward_segments(x, taus, hidden, reset)
         fast = self._canonical() if self.fast_host else None
         lazy = False
         if hidden is None:

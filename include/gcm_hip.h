@@ -1091,6 +1091,10 @@ int gcm_dense_rollout_tp_fwd(const float* obs, const gcm_selector_desc* selector
  * Declared in gcm_hip_window.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_window.h"
 
+/* ---- episode resets inside one SparseGCM call: SparseGCM.rollout(x, reset=mask) (csrc/sparse_segments.hip) ----
+ * Declared in gcm_hip_segments.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_segments.h"
+
 /* ---- time-parallel DenseGCM rollout with EuclideanEdge (round 5; csrc/euclid_tp.hip) ----------------------------
  * DenseGCM.rollout(obs [T,B,F]) from EMPTY graphs with EuclideanEdge (edge_selectors/distance.py:18-49: the mean over
  * the B graphs' current nodes of the distance to a stored node, threshold max_distance; dist_param: the `learned`
