@@ -526,8 +526,10 @@ def khop_mask(graph, node_off, T, taus, hops, B, t_pad):
     M = graph.M
     mask = torch.empty(M, dtype=torch.uint8, device=graph.row_ptr.device)
     scratch = torch.empty(2 * M, dtype=torch.uint8, device=mask.device)
+    # (a list without edges - the first one-node call of a stepwise run - has no col array to walk: the subgraph is the
+    #  new nodes themselves, which is what 0 rounds leave)
     _call("gcm_khop_mask", _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(node_off),
-          _hip.ptr(T), _hip.ptr(taus), hops, _hip.ptr(mask), _hip.ptr(scratch), M, B, t_pad,
+          _hip.ptr(T), _hip.ptr(taus), hops if graph.E else 0, _hip.ptr(mask), _hip.ptr(scratch), M, B, t_pad,
           _hip.stream())
     return mask
 
@@ -1912,6 +1914,108 @@ class _CsrGENAgg(torch.autograd.Function):
 
 def csr_genagg(xs, t, graph, eps=1e-7):
     return _CsrGENAgg.apply(xs, t, graph, float(eps))
+
+
+# ---------------------------------------------------------------------------
+# EdgeConv / DenseEdgeConv (PyG, aggr="max"; csrc/edgeconv.hip): the per-edge stage - activation, second Linear and the
+# running max with its winner.  The two node-level products P, Q of the first Linear stay in torch.
+# ---------------------------------------------------------------------------
+def _edgemax_operands(P, Q, w2, b2):
+    P, Q, w2, b2 = P.contiguous(), Q.contiguous(), w2.contiguous(), _contig(b2)
+    _hip.on_device(P, Q, w2, b2)
+    assert P.dtype == _f32 and Q.dtype == _f32 and w2.dtype == _f32, "the EdgeConv kernels are float32 only"
+    assert P.shape == Q.shape and w2.dim() == 2 and w2.shape[1] == P.shape[-1], "P, Q [.., H], W2 [C, H]"
+    assert b2 is None or (b2.dtype == _f32 and b2.shape == (w2.shape[0],))
+    return P, Q, w2, b2
+
+
+def _edgemax_grads(ctx, slots, P, w2, b2_shape):
+    """(g_P, g_Q, g_w2, g_b2): a fresh tensor for every input that needs a gradient, None (= skipped by the kernels) for
+    the others; slots: the positions of P, Q, W2, b2 among the inputs."""
+    need_p, need_q, need_w, need_b = (ctx.needs_input_grad[i] for i in slots)
+    return (torch.empty_like(P) if need_p else None, torch.empty_like(P) if need_q else None,
+            torch.empty_like(w2) if need_w else None,
+            torch.empty(b2_shape, device=P.device, dtype=_f32) if need_b and b2_shape is not None else None)
+
+
+class _DenseEdgeMax(torch.autograd.Function):
+    """out_ic = max over {j: adj[b,i,j] != 0} of (W2 leaky_relu(P_i + Q_j) + b2)_c, 0 for an empty row; P, Q [B,N,H],
+    adj [B,N,N] (pattern only: no gradient).  -> (out [B,N,C], winner [B,N,C] int32: the source index, -1 for none)."""
+    @staticmethod
+    def forward(ctx, P, Q, adj, w2, b2, slope):
+        P, Q, w2, b2 = _edgemax_operands(P, Q, w2, b2)
+        adj = adj.contiguous()
+        _hip.on_device(adj)
+        B, N, H = P.shape
+        C = w2.shape[0]
+        assert adj.shape == (B, N, N) and adj.dtype == _f32, "adj must be float32 [B, N, N]"
+        out = torch.empty(B, N, C, device=P.device, dtype=_f32)
+        winner = torch.empty(B, N, C, device=P.device, dtype=torch.int32)
+        _call("gcm_dense_edgemax_fwd", _hip.ptr(P), _hip.ptr(Q), _hip.ptr(adj), _hip.ptr(w2), _hip.ptr(b2), slope,
+              _hip.ptr(out), _hip.ptr(winner), B, N, H, C, _hip.stream())
+        ctx.save_for_backward(P, Q, w2, winner)
+        ctx.slope, ctx.b2_shape = slope, None if b2 is None else b2.shape
+        ctx.mark_non_differentiable(winner)
+        return out, winner
+
+    @staticmethod
+    def backward(ctx, g_out, _):
+        P, Q, w2, winner = ctx.saved_tensors
+        B, N, H = P.shape
+        C = w2.shape[0]
+        g_out = g_out.contiguous()
+        g_P, g_Q, g_w2, g_b2 = _edgemax_grads(ctx, (0, 1, 3, 4), P, w2, ctx.b2_shape)
+        ws, ws_bytes = (_scratch("gcm_dense_edgemax_bwd", B, N, H, C, device=P.device)
+                        if g_w2 is not None or g_b2 is not None else (None, 0))
+        _call("gcm_dense_edgemax_bwd", _hip.ptr(g_out), _hip.ptr(P), _hip.ptr(Q), _hip.ptr(winner), _hip.ptr(w2),
+              ctx.slope, _hip.ptr(g_P), _hip.ptr(g_Q), _hip.ptr(g_w2), _hip.ptr(g_b2), _hip.ptr(ws), ws_bytes, B, N, H,
+              C, _hip.stream())
+        return g_P, g_Q, None, g_w2, g_b2, None
+
+
+def dense_edgemax(P, Q, adj, W2, b2, slope, with_winner=False):
+    out, winner = _DenseEdgeMax.apply(P, Q, adj.detach(), W2, b2, float(slope))
+    return (out, winner) if with_winner else out
+
+
+class _CsrEdgeMax(torch.autograd.Function):
+    """The same over the in-edges of every node of `graph` (every CSR entry competes on its own); P, Q [M,H].
+    -> (out [M,C], winner [M,C] int32: the CSR position of the winning entry, -1 for none)."""
+    @staticmethod
+    def forward(ctx, P, Q, w2, b2, slope, graph):
+        P, Q, w2, b2 = _edgemax_operands(P, Q, w2, b2)
+        M, H = P.shape
+        C = w2.shape[0]
+        assert M == graph.M
+        out = torch.empty(M, C, device=P.device, dtype=_f32)
+        winner = torch.empty(M, C, device=P.device, dtype=torch.int32)
+        _call("gcm_csr_edgemax_fwd", _hip.ptr(P), _hip.ptr(Q), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(w2), _hip.ptr(b2), slope, _hip.ptr(out), _hip.ptr(winner), M, graph.E, H, C, _hip.stream())
+        ctx.save_for_backward(P, Q, w2, winner)
+        ctx.slope, ctx.b2_shape, ctx.graph = slope, None if b2 is None else b2.shape, graph
+        ctx.mark_non_differentiable(winner)
+        return out, winner
+
+    @staticmethod
+    def backward(ctx, g_out, _):
+        P, Q, w2, winner = ctx.saved_tensors
+        graph = ctx.graph
+        M, H = P.shape
+        C, E = w2.shape[0], graph.E
+        g_out = g_out.contiguous()
+        g_P, g_Q, g_w2, g_b2 = _edgemax_grads(ctx, (0, 1, 2, 3), P, w2, ctx.b2_shape)
+        col_ptr, rows, perm = _csc_or_none(graph, g_Q is not None and E > 0)
+        ws, ws_bytes = (_scratch("gcm_csr_edgemax_bwd", M, E, H, C, device=P.device)
+                        if g_w2 is not None or g_b2 is not None else (None, 0))
+        _call("gcm_csr_edgemax_bwd", _hip.ptr(g_out), _hip.ptr(P), _hip.ptr(Q), _hip.ptr(winner), _hip.ptr(graph.col),
+              _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w2), ctx.slope, _hip.ptr(g_P), _hip.ptr(g_Q),
+              _hip.ptr(g_w2), _hip.ptr(g_b2), _hip.ptr(ws), ws_bytes, M, E, H, C, _hip.stream())
+        return g_P, g_Q, g_w2, g_b2, None, None
+
+
+def csr_edgemax(P, Q, W2, b2, slope, graph, with_winner=False):
+    out, winner = _CsrEdgeMax.apply(P, Q, W2, b2, float(slope), graph)
+    return (out, winner) if with_winner else out
 
 
 # ===========================================================================

@@ -1176,6 +1176,102 @@ class GENConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, aggr={self.aggr})"
 
 
+_EDGE_NN_FORM = ("torch.nn.Sequential(Linear(2 * F, H), ReLU() or LeakyReLU(s), Linear(H, C)); a monotone activation "
+                 "behind the last Linear commutes with the max and can follow the layer instead")
+
+
+def _edge_init(conv, name, nn, aggr):
+    if aggr != "max":
+        raise NotImplementedError(f"{name}(aggr={aggr!r}) is not implemented: 'max' only, with nn = {_EDGE_NN_FORM}")
+    ok = (isinstance(nn, torch.nn.Sequential) and len(nn) == 3 and isinstance(nn[0], torch.nn.Linear)
+          and isinstance(nn[1], (torch.nn.ReLU, torch.nn.LeakyReLU)) and isinstance(nn[2], torch.nn.Linear)
+          and nn[0].in_features % 2 == 0 and nn[0].out_features == nn[2].in_features)
+    if not ok:
+        raise NotImplementedError(f"{name}: this nn is not implemented; the accepted form is {_EDGE_NN_FORM}")
+    conv.nn, conv.aggr = nn, aggr
+    conv.in_channels, conv.out_channels = nn[0].in_features // 2, nn[2].out_features
+
+
+def _edge_terms(conv, x):
+    """(P, Q, W2, b2, slope): the first Linear as two node-level products (torch), W1 = [A | Bm]:
+    W1 [x_i, x_j - x_i] + b1 = P_i + Q_j with P = x (A - Bm)^T + b1, Q = x Bm^T."""
+    lin1, act, lin2 = conv.nn[0], conv.nn[1], conv.nn[2]
+    F = x.shape[-1]
+    if lin1.in_features != 2 * F:
+        raise ValueError(f"nn[0] takes {lin1.in_features} features, but [x_i, x_j - x_i] has 2 * {F}")
+    _hip.on_device(x, lin2.weight)          # a CPU call fails here, before any torch op runs
+    if x.dtype != torch.float32:
+        raise TypeError("x must be float32; got %s" % x.dtype)
+    A, Bm = lin1.weight[:, :F], lin1.weight[:, F:]
+    P = torch.nn.functional.linear(x, A - Bm, lin1.bias)
+    Q = torch.nn.functional.linear(x, Bm)
+    slope = act.negative_slope if isinstance(act, torch.nn.LeakyReLU) else 0.0
+    return P, Q, lin2.weight, lin2.bias, slope
+
+
+_EDGE_DOC = """x_i' = max over the in-neighbours j of i of nn([x_i, x_j - x_i]), per channel (Wang et al., Dynamic
+    Graph CNN): the one layer here whose message depends on the relative feature x_j - x_i.  `nn` must be a
+    torch.nn.Sequential of exactly Linear(2F -> H), ReLU() or LeakyReLU(s), Linear(H -> C) (subclasses of Linear such
+    as SkinnyLinear count, biases are optional): state_dict keys `nn.0.weight`, `nn.0.bias`, `nn.2.weight`,
+    `nn.2.bias`, PyG's own.  With nn.0.weight = [A | Bm] the first Linear is two node-level products, P = x (A - Bm)^T
+    + b1 and Q = x Bm^T (torch, under autograd); the per-edge stage act(P_i + Q_j), the second Linear and the running
+    max with its winner are HIP kernels (csrc/edgeconv.hip) that write neither the hidden activations nor the messages
+    to memory; the gradient flows through the winning edge of every (node, channel) alone.  A node without in-edges
+    gets 0 and sends no gradient.  Of bitwise equal messages the first wins: the lowest source index (dense), the first
+    edge of the node in the list's order (sparse).  float32, H and C up to 128.  Not implemented
+    (NotImplementedError at construction): any other nn - a single Linear, a trailing activation, norm layers inside
+    the MLP, deeper MLPs - and any aggr but "max"; a monotone activation behind the last Linear commutes with the max
+    and can follow the layer.  nn[0].in_features != 2 * x.shape[-1] raises ValueError at the call."""
+
+
+class DenseEdgeConv(torch.nn.Module):
+    __doc__ = """PyG's EdgeConv on a dense adjacency, which PyG does not have: x [B,N,F] or [N,F], adj [B,N,N],
+    [1,N,N] or [N,N] float32 (adj[b,i,j] != 0: i receives from j).  Only the pattern of adj is read: its values do not
+    matter and it gets no gradient; the diagonal is an ordinary entry (x_j - x_i = 0) and no loop is added.  The
+    output is multiplied by the mask.
+    """ + _EDGE_DOC + """  Loads EdgeConv's state_dict.  Not a DenseGraphConv: DenseGCM runs a stack of these through
+    its layered path."""
+
+    def __init__(self, nn, aggr="max"):
+        super().__init__()
+        _edge_init(self, "DenseEdgeConv", nn, aggr)
+
+    def reset_parameters(self):
+        _gin_reset(self.nn)
+
+    def forward(self, x, adj, mask=None):
+        x, adj = _dense_inputs(x, adj)
+        P, Q, w2, b2, slope = _edge_terms(self, x)
+        return _masked(_ops.dense_edgemax(P, Q, adj, w2, b2, slope), mask, x)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(nn={self.nn})"
+
+
+class EdgeConv(torch.nn.Module):
+    __doc__ = """PyG's EdgeConv (flow source_to_target): edge_index [2,E] = (source, sink), x [M,F].  The edges are
+    used as given: no loop is added or removed, an i -> i edge is an ordinary entry with x_j - x_i = 0, duplicate
+    edges compete separately.  Uses the `edge_index.gcm_graph` index SparseGCM attaches; any other edge list is indexed
+    here.  DynamicEdgeConv is not provided: KNNEdge / SpatialKNNEdge + EdgeConv is the memory's form of it.
+    """ + _EDGE_DOC + """  Loads DenseEdgeConv's state_dict.  Not a GraphConv: SparseGCM runs a stack of these through
+    its generic path."""
+
+    def __init__(self, nn, aggr="max"):
+        super().__init__()
+        _edge_init(self, "EdgeConv", nn, aggr)
+
+    def reset_parameters(self):
+        _gin_reset(self.nn)
+
+    def forward(self, x, edge_index):
+        P, Q, w2, b2, slope = _edge_terms(self, x)
+        graph = _graph_of(x, edge_index, "EdgeConv")
+        return _ops.csr_edgemax(P, Q, w2, b2, slope, graph)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(nn={self.nn})"
+
+
 class Sequential(torch.nn.Module):
     """Stand-in for torch_geometric.nn.Sequential: a chain of modules wired by
     name, e.g. Sequential("x, adj, weights, B, N", [(conv, "x, adj -> x"), Tanh()]).
