@@ -32,62 +32,31 @@ struct Lin2Args {
 
 template <int NCT>
 __global__ __launch_bounds__(256) void k_aggr_lin2(Lin2Args p) {
-  constexpr int NC = 32 * NCT;
-  __shared__ float sA[MB * (KT + 1)];  // [i][k]
-  __shared__ float sB[KT * (NC + 1)];  // [k][j]
+  __shared__ float sA[MB * (KT + 1)];        // [i][k]
+  __shared__ float sB[KT * (32 * NCT + 1)];  // [k][j]
   const int i0 = blockIdx.x * MB;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  const TileLane t = tile_lane();
   f32x16 acc[NCT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
+  tile_zero(acc);
   for (int seg = 0; seg < p.nseg; ++seg) {
     const float* A = p.A[seg];
     const float* B = p.B[seg];
     const int K = p.K[seg];
     const int64_t bks = p.b_ks[seg], bjs = p.b_js[seg];
-    const bool b_kfast = bks == 1;
-    for (int k0 = 0; k0 < K; k0 += KT) {
-      for (int e = threadIdx.x; e < MB * KT; e += 256) {
-        const int r = e / KT, k = e % KT;
-        const int gi = i0 + r, gk = k0 + k;
-        sA[r * (KT + 1) + k] = (gi < p.M && gk < K) ? A[(size_t)gi * K + gk] : 0.f;
-      }
-      for (int e = threadIdx.x; e < KT * NC; e += 256) {
-        const int k = b_kfast ? e % KT : e / NC, j = b_kfast ? e / KT : e % NC;
-        const int gk = k0 + k;
-        sB[k * (NC + 1) + j] = (gk < K && j < p.N) ? B[(size_t)gk * bks + (size_t)j * bjs] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NCT; ++c)
-        mma32(acc[c], sA + wave * 32 * (KT + 1), KT + 1, 1, sB + c * 32, NC + 1, 1, KT, li, lh);
-      __syncthreads();
-    }
+    tile_mma<NCT, false>(
+        acc, t, sA, sB, i0, 0, p.M, p.N, 0, K, false, bks == 1,
+        [=](int gi, int gk) { return A[(size_t)gi * K + gk]; },
+        [=](int gk, int gj) { return B[(size_t)gk * bks + (size_t)gj * bjs]; });
   }
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int j = c * 32 + li;
-    if (j >= p.N) continue;
+  tile_store(acc, t, i0, 0, p.M, p.N, [=](int j) {
     const float bias = p.bias ? p.bias[j] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = i0 + wave * 32 + acc_row(r, lh);
-      if (i < p.M) p.C[(size_t)i * p.N + j] = acc[c][r] + bias;
-    }
-  }
+    return [=](int i, float v) { p.C[(size_t)i * p.N + j] = v + bias; };
+  });
 }
 
 int launch_lin2(const Lin2Args& p, hipStream_t s) {  // N <= 128
-  const dim3 grid((p.M + MB - 1) / MB);
-  switch ((p.N + 31) / 32) {
-    case 1: hipLaunchKernelGGL(k_aggr_lin2<1>, grid, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(k_aggr_lin2<2>, grid, dim3(256), 0, s, p); break;
-    case 3: hipLaunchKernelGGL(k_aggr_lin2<3>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(k_aggr_lin2<4>, grid, dim3(256), 0, s, p); break;
-  }
+  const dim3 grid(blocks(p.M, MB));
+  dispatch_nct(nct_of(p.N), [&](auto n) { hipLaunchKernelGGL(k_aggr_lin2<n()>, grid, dim3(256), 0, s, p); });
   return gcm_launch_status();
 }
 
@@ -364,12 +333,9 @@ extern "C" int gcm_dense_aggrconv_fwd(const float* x, const float* adj, const fl
     if ((rc = launch_mm(p, 1, s))) return rc;
   } else {
     const dim3 grid(blocks(N, XR), B);
-    switch ((Fi + 31) / 32) {
-      case 1: hipLaunchKernelGGL(k_aggr_dense_max_fwd<1>, grid, dim3(256), 0, s, x, adj, agg, winner, N, Fi); break;
-      case 2: hipLaunchKernelGGL(k_aggr_dense_max_fwd<2>, grid, dim3(256), 0, s, x, adj, agg, winner, N, Fi); break;
-      case 3: hipLaunchKernelGGL(k_aggr_dense_max_fwd<3>, grid, dim3(256), 0, s, x, adj, agg, winner, N, Fi); break;
-      default: hipLaunchKernelGGL(k_aggr_dense_max_fwd<4>, grid, dim3(256), 0, s, x, adj, agg, winner, N, Fi); break;
-    }
+    dispatch_nct((Fi + 31) / 32, [&](auto n) {
+      hipLaunchKernelGGL(k_aggr_dense_max_fwd<n()>, grid, dim3(256), 0, s, x, adj, agg, winner, N, Fi);
+    });
     if ((rc = gcm_launch_status())) return rc;
   }
   return linear_fwd(agg, x, w_rel, w_root, bias, out, rows, Fi, Fo, s);
@@ -451,12 +417,9 @@ extern "C" int gcm_dense_aggrconv_bwd(const float* g_out, const float* x, const 
   if (w_root && (rc = mm_gw(g_out, w_root, g_x, rows, Fi, Fo, s))) return rc;       // the root term
   const dim3 grid(blocks(N, XR), B);
   const int accumulate = w_root != nullptr;
-  switch ((Fi + 31) / 32) {
-    case 1: hipLaunchKernelGGL(k_aggr_dense_max_bwd<1>, grid, dim3(256), 0, s, t, winner, g_x, N, Fi, accumulate); break;
-    case 2: hipLaunchKernelGGL(k_aggr_dense_max_bwd<2>, grid, dim3(256), 0, s, t, winner, g_x, N, Fi, accumulate); break;
-    case 3: hipLaunchKernelGGL(k_aggr_dense_max_bwd<3>, grid, dim3(256), 0, s, t, winner, g_x, N, Fi, accumulate); break;
-    default: hipLaunchKernelGGL(k_aggr_dense_max_bwd<4>, grid, dim3(256), 0, s, t, winner, g_x, N, Fi, accumulate); break;
-  }
+  dispatch_nct((Fi + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_aggr_dense_max_bwd<n()>, grid, dim3(256), 0, s, t, winner, g_x, N, Fi, accumulate);
+  });
   return gcm_launch_status();
 }
 

@@ -54,7 +54,6 @@ __device__ __forceinline__ void wave_sync() {
 }
 __device__ __forceinline__ float leaky(float v, float s) { return v > 0.f ? v : v * s; }
 __device__ __forceinline__ float dleaky(float v, float s) { return v > 0.f ? 1.f : s; }
-__device__ __forceinline__ int first_bit(unsigned long long mask) { return __ffsll((long long)mask) - 1; }
 // lanes over k: the power of two >= H (16 at least), as a shift; the other lane bits split rows or channels
 __device__ __forceinline__ int width_shift(int H) { return H <= 16 ? 4 : H <= 32 ? 5 : 6; }
 
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(TPB) void k_edgemax_bwd_q_dense(const float* __rest
     for (int u = 0; u < SW; ++u) {
       unsigned long long mask = __ballot(v[u] == jl);
       while (mask) {
-        const int th = t0 + 64 * u + first_bit(mask);
+        const int th = t0 + 64 * u + gcm_first_bit(mask);
         mask &= mask - 1;
         const int il = th / C, c = th - il * C;
         q_term(acc, lane, gb[th], P + (base + il) * H, q, w2 + (int64_t)c * H, slope, H);
@@ -330,7 +329,7 @@ __global__ __launch_bounds__(TPB) void k_edgemax_bwd_q_csr(const float* __restri
       const int c = cb + lane;
       unsigned long long mask = __ballot(c < C && winner[i * C + c] == e);
       while (mask) {
-        const int ch = cb + first_bit(mask);
+        const int ch = cb + gcm_first_bit(mask);
         mask &= mask - 1;
         q_term(acc, lane, g[i * C + ch], P + i * H, q, w2 + (int64_t)ch * H, slope, H);
       }

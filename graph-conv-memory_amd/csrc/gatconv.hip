@@ -21,7 +21,7 @@
 // atomics: every sum runs in a fixed order.  Fi, H*C <= 128; any N.
 #include <cmath>
 
-#include "attn_bits.h"  // GT, k_gat_mask_bits
+#include "attn_bits.h"  // GT, mask_bits
 
 namespace {
 
@@ -541,16 +541,13 @@ extern "C" int gcm_dense_gatconv_fwd(const float* x, const float* adj, const flo
   if (unsupported(R, Fi, H, C) || B > 65535) return GCM_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int W = (N + 31) / 32;
-  hipLaunchKernelGGL(k_gat_mask_bits, dim3(blocks(R, 4)), dim3(256), 0, s, adj, bits, R, N, W, add_loop);
-  int rc = gcm_launch_status();
+  int rc = mask_bits(adj, bits, R, N, W, add_loop, s);
   if (rc || (rc = fwd_head(x, w, att_src, att_dst, y, s_src, s_dst, R, Fi, H, C, s))) return rc;
   const dim3 grid(dense_blocks(N), B);
-  switch ((C + 31) / 32) {
-    case 1: hipLaunchKernelGGL(k_gat_dense_fwd<1>, grid, dim3(256), 0, s, bits, y, s_src, s_dst, o, row_m, row_l, N, H, C, negative_slope); break;
-    case 2: hipLaunchKernelGGL(k_gat_dense_fwd<2>, grid, dim3(256), 0, s, bits, y, s_src, s_dst, o, row_m, row_l, N, H, C, negative_slope); break;
-    case 3: hipLaunchKernelGGL(k_gat_dense_fwd<3>, grid, dim3(256), 0, s, bits, y, s_src, s_dst, o, row_m, row_l, N, H, C, negative_slope); break;
-    default: hipLaunchKernelGGL(k_gat_dense_fwd<4>, grid, dim3(256), 0, s, bits, y, s_src, s_dst, o, row_m, row_l, N, H, C, negative_slope); break;
-  }
+  dispatch_nct((C + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_gat_dense_fwd<n()>, grid, dim3(256), 0, s, bits, y, s_src, s_dst, o, row_m, row_l, N, H, C,
+                       negative_slope);
+  });
   if ((rc = gcm_launch_status())) return rc;
   return fwd_tail(o, bias, out, R, H, C, concat, s);
 }
@@ -589,16 +586,14 @@ extern "C" int gcm_dense_gatconv_bwd(const float* g_out, const float* x, const f
   float* gss = (float*)(ws + L.gss);
   float* dl = (float*)(ws + L.delta);
   for (int pass = 0; pass < 2; ++pass) {  // delta = sum_j P dP, then the gradients
-    switch ((C + 31) / 32 + 4 * (pass == 0)) {
-      case 1: hipLaunchKernelGGL((k_gat_dense_bwd<1, false>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 2: hipLaunchKernelGGL((k_gat_dense_bwd<2, false>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 3: hipLaunchKernelGGL((k_gat_dense_bwd<3, false>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 4: hipLaunchKernelGGL((k_gat_dense_bwd<4, false>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 5: hipLaunchKernelGGL((k_gat_dense_bwd<1, true>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 6: hipLaunchKernelGGL((k_gat_dense_bwd<2, true>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      case 7: hipLaunchKernelGGL((k_gat_dense_bwd<3, true>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-      default: hipLaunchKernelGGL((k_gat_dense_bwd<4, true>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO, dl, att_src, gy, gss, part, N, H, C, negative_slope); break;
-    }
+    dispatch_nct((C + 31) / 32, [&](auto n) {
+      if (pass == 0)
+        hipLaunchKernelGGL((k_gat_dense_bwd<n(), true>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO,
+                           dl, att_src, gy, gss, part, N, H, C, negative_slope);
+      else
+        hipLaunchKernelGGL((k_gat_dense_bwd<n(), false>), grid, dim3(256), 0, s, bits, y, s_src, s_dst, row_m, row_l, dO,
+                           dl, att_src, gy, gss, part, N, H, C, negative_slope);
+    });
     if ((rc = gcm_launch_status())) return rc;
     if (pass == 0) {
       hipLaunchKernelGGL(k_gat_sum_parts, dim3(blocks(R * H, 256)), dim3(256), 0, s, part, nblk, N, dl, R, H);

@@ -330,58 +330,29 @@ struct GgMm {
 
 template <int NCT>
 __global__ __launch_bounds__(256) void k_gg_mm(GgMm p) {
-  constexpr int NC = 32 * NCT;
-  __shared__ float sA[MB * (KT + 1)];  // [i][k]
-  __shared__ float sB[KT * (NC + 1)];  // [k][j]
+  __shared__ float sA[MB * (KT + 1)];        // [i][k]
+  __shared__ float sB[KT * (32 * NCT + 1)];  // [k][j]
   const int b = blockIdx.z;
-  const int i0 = blockIdx.x * MB, j0 = blockIdx.y * NC;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  const int i0 = blockIdx.x * MB, j0 = blockIdx.y * 32 * NCT;
+  const TileLane t = tile_lane();
   const float* Ab = p.A + (size_t)b * p.a_bs;
   const float* Bb = p.B + (size_t)b * p.b_bs;
   const bool b_kfast = p.b_ks == 1 && p.b_js != 1;
-
   f32x16 acc[NCT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-  for (int k0 = 0; k0 < p.K; k0 += KT) {
-    for (int e = threadIdx.x; e < MB * KT; e += 256) {
-      const int r = e / KT, k = e % KT;
-      const int gi = i0 + r, gk = k0 + k;
-      float v = 0.f;
-      if (gi < p.M && gk < p.K) v = Ab[(size_t)gi * p.lda + (gk < p.a_split ? gk : gk + p.a_skip)];
-      sA[r * (KT + 1) + k] = v;
-    }
-    for (int e = threadIdx.x; e < KT * NC; e += 256) {
-      const int k = b_kfast ? e % KT : e / NC, j = b_kfast ? e / KT : e % NC;
-      const int gk = k0 + k, gj = j0 + j;
-      sB[k * (NC + 1) + j] = (gk < p.K && gj < p.N) ? Bb[(size_t)gk * p.b_ks + (size_t)gj * p.b_js] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-      mma32(acc[c], sA + wave * 32 * (KT + 1), KT + 1, 1, sB + c * 32, NC + 1, 1, KT, li, lh);
-    __syncthreads();
-  }
-
+  tile_zero(acc);
+  tile_mma<NCT, false>(
+      acc, t, sA, sB, i0, j0, p.M, p.N, 0, p.K, false, b_kfast,
+      [=](int gi, int gk) { return Ab[(size_t)gi * p.lda + (gk < p.a_split ? gk : gk + p.a_skip)]; },
+      [=](int gk, int gj) { return Bb[(size_t)gk * p.b_ks + (size_t)gj * p.b_js]; });
   const size_t cb = (size_t)b * p.c_bs;
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int j = j0 + c * 32 + li;
-    if (j >= p.N) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = i0 + wave * 32 + acc_row(r, lh);
-      if (i >= p.M) continue;
+  tile_store(acc, t, i0, j0, p.M, p.N, [=](int j) {
+    return [=](int i, float v) {
       const size_t off = cb + (size_t)i * p.ldc + j;
-      float v = acc[c][r];
       if (p.add) v = p.mul ? fmaf(p.add[off], p.mul[off], v) : v + p.add[off];
       if (p.zero_diag && i == j) v = 0.f;
       p.C[off] = v;
-    }
-  }
+    };
+  });
 }
 
 GgMm gg_mm_args() {
@@ -391,15 +362,9 @@ GgMm gg_mm_args() {
 }
 
 int gg_launch_mm(const GgMm& p, int batch, hipStream_t s) {
-  const int nct = p.N > 96 ? 4 : (p.N > 64 ? 3 : (p.N > 32 ? 2 : 1));
-  const int NC = 32 * nct;
-  const dim3 grid((p.M + MB - 1) / MB, (p.N + NC - 1) / NC, batch);
-  switch (nct) {
-    case 1: hipLaunchKernelGGL(k_gg_mm<1>, grid, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(k_gg_mm<2>, grid, dim3(256), 0, s, p); break;
-    case 3: hipLaunchKernelGGL(k_gg_mm<3>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(k_gg_mm<4>, grid, dim3(256), 0, s, p); break;
-  }
+  const int nct = nct_of(p.N);
+  const dim3 grid(blocks(p.M, MB), blocks(p.N, 32 * nct), batch);
+  dispatch_nct(nct, [&](auto n) { hipLaunchKernelGGL(k_gg_mm<n()>, grid, dim3(256), 0, s, p); });
   return gcm_launch_status();
 }
 
@@ -653,8 +618,7 @@ extern "C" int gcm_dense_gatedgraphconv_fwd(const float* x, const float* adj, co
   hipStream_t s = (hipStream_t)stream;
   float* sv = (float*)saved;
   unsigned* bits = (unsigned*)(sv + (size_t)SLOTS * L * R * C);
-  hipLaunchKernelGGL(k_gat_mask_bits, dim3(blocks(R, 4)), dim3(256), 0, s, adj, bits, R, N, W, add_loop);
-  const int rc = gcm_launch_status();
+  const int rc = mask_bits(adj, bits, R, N, W, add_loop, s);
   if (rc) return rc;
   Nbr g = {};
   g.bits = bits, g.adj = adj, g.N = N, g.W = W, g.add_loop = add_loop;
@@ -684,8 +648,7 @@ extern "C" int gcm_dense_gatedgraphconv_bwd(const float* g_out, const float* adj
   const float* sv = (const float*)saved;
   const unsigned* bits = (const unsigned*)(sv + (size_t)SLOTS * L * R * C);
   unsigned* bitsT = (unsigned*)((char*)workspace + K.bitsT);
-  hipLaunchKernelGGL(k_mask_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
-  const int rc = gcm_launch_status();
+  const int rc = mask_bits_t(bits, bitsT, R, N, W, s);
   if (rc) return rc;
   Nbr gt = {};
   gt.bits = bitsT, gt.adj = adj, gt.N = N, gt.W = W, gt.add_loop = add_loop, gt.tr = 1;

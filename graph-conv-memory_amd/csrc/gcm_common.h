@@ -82,6 +82,8 @@ __device__ __forceinline__ float gcm_xor32_add(float v) {
   const gcm_u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// the lowest set bit of a ballot (-1: none)
+__device__ __forceinline__ int gcm_first_bit(unsigned long long mask) { return __ffsll((long long)mask) - 1; }
 __device__ __forceinline__ float gcm_wave_max(float v) {
   v = fmaxf(v, GCM_DPP_F(v, 0xB1, 0xF, v));
   v = fmaxf(v, GCM_DPP_F(v, 0x4E, 0xF, v));

@@ -356,12 +356,10 @@ extern "C" int gcm_csr_gcnconv_fwd(const float* x, const int64_t* row_ptr, const
   if (Fi > 128 || Fo > 128) return GCM_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(blocks(M, MB));
-  switch ((Fi + 31) / 32) {
-    case 1: hipLaunchKernelGGL(k_gcn_csr_fwd<1>, grid, dim3(256), 0, s, x, row_ptr, col, coef, loop_coef, w, bias, out, agg, M, Fi, Fo); break;
-    case 2: hipLaunchKernelGGL(k_gcn_csr_fwd<2>, grid, dim3(256), 0, s, x, row_ptr, col, coef, loop_coef, w, bias, out, agg, M, Fi, Fo); break;
-    case 3: hipLaunchKernelGGL(k_gcn_csr_fwd<3>, grid, dim3(256), 0, s, x, row_ptr, col, coef, loop_coef, w, bias, out, agg, M, Fi, Fo); break;
-    default: hipLaunchKernelGGL(k_gcn_csr_fwd<4>, grid, dim3(256), 0, s, x, row_ptr, col, coef, loop_coef, w, bias, out, agg, M, Fi, Fo); break;
-  }
+  dispatch_nct((Fi + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_gcn_csr_fwd<n()>, grid, dim3(256), 0, s, x, row_ptr, col, coef, loop_coef, w, bias, out, agg,
+                       M, Fi, Fo);
+  });
   return gcm_launch_status();
 }
 

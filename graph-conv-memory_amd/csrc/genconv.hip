@@ -29,7 +29,7 @@
 // order.  Every sum has one order: results are bitwise reproducible.  C <= 128.
 #include <algorithm>
 
-#include "gcm_common.h"
+#include "fixed_sum.h"
 
 namespace {
 
@@ -93,22 +93,9 @@ struct Moments {
   }
 };
 
-// sum of the 256 per-thread values in a fixed order (every thread of the workgroup calls it)
-__device__ __forceinline__ double block_sum(double s, double* sp) {
-  sp[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = TPB / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sp[threadIdx.x] += sp[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sp[0];
-}
-
 // ---------------------------------------------------------------------------
 // dense: one wave per row
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int first_bit(unsigned long long mask) { return __ffsll((long long)mask) - 1; }
-
 __global__ __launch_bounds__(TPB) void k_gen_dense_fwd(const float* __restrict__ xs, const float* __restrict__ adj,
                                                        const float* __restrict__ t_ptr, float eps,
                                                        float* __restrict__ agg, float* __restrict__ lse,
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(TPB) void k_gen_dense_fwd(const float* __restrict__
     unsigned long long mask = __ballot(v != 0.f);
     if (lane == 0) bits[i * W64 + w] = (int64_t)mask;
     while (mask) {
-      const float* xr = xs + (base + k0 + first_bit(mask)) * C;
+      const float* xr = xs + (base + k0 + gcm_first_bit(mask)) * C;
       mask &= mask - 1;
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(TPB) void k_gen_dense_bwd_x(const float* __restrict
     const unsigned long long u = k < N ? (unsigned long long)bits[(b0 + k) * W64 + word] : 0ull;
     unsigned long long mask = __ballot((int)((u >> bit) & 1ull));
     while (mask) {
-      const int64_t i = b0 + k0 + first_bit(mask);
+      const int64_t i = b0 + k0 + gcm_first_bit(mask);
       mask &= mask - 1;
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
@@ -213,7 +200,7 @@ __global__ __launch_bounds__(TPB) void k_gen_dense_gt_parts(const float* __restr
     for (int w = 0; w < W64; ++w) {
       unsigned long long mask = (unsigned long long)bits[i * W64 + w];  // the same word for the whole wave
       while (mask) {
-        const float* xr = xs + (base + 64 * w + first_bit(mask)) * C;
+        const float* xr = xs + (base + 64 * w + gcm_first_bit(mask)) * C;
         mask &= mask - 1;
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) {
@@ -307,16 +294,6 @@ __global__ __launch_bounds__(TPB) void k_gen_csr_gt_parts(const float* __restric
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
-// g_t, pass 2 (one workgroup): out[0] = sum of the n partials in a fixed order
-__global__ __launch_bounds__(TPB) void k_gen_gt_final(const double* __restrict__ part, int n,
-                                                      float* __restrict__ out) {
-  __shared__ double sp[TPB];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += TPB) s += part[i];
-  const double total = block_sum(s, sp);
-  if (threadIdx.x == 0) out[0] = (float)total;
-}
-
 // the g_t partials: at most GT_BLOCKS of them
 constexpr int GT_BLOCKS = 4096;
 
@@ -353,11 +330,6 @@ size_t dense_gt_ws_bytes(int64_t rows) {
 unsigned grid_of(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 bool too_large(int64_t rows, int C) { return C > 64 * SLOTS || rows > (1 << 30); }
-
-int gt_final(const double* part, int n, float* g_t, hipStream_t s) {
-  hipLaunchKernelGGL(k_gen_gt_final, dim3(1), dim3(TPB), 0, s, part, n, g_t);
-  return gcm_launch_status();
-}
 
 }  // namespace
 
@@ -402,7 +374,7 @@ extern "C" int gcm_dense_gen_bwd(const float* g_agg, const float* xs, const int6
     hipLaunchKernelGGL(k_gen_dense_gt_parts, dim3(n), dim3(TPB), 0, s, g_agg, xs, bits, t, eps, lse, rows, N, C, r,
                        part);
     if ((rc = gcm_launch_status())) return rc;
-    if ((rc = gt_final(part, n, g_t, s))) return rc;
+    if ((rc = sum_parts(part, n, g_t, s))) return rc;
   }
   return GCM_OK;
 }
@@ -452,7 +424,7 @@ extern "C" int gcm_csr_gen_bwd(const float* g_agg, const float* xs, const float*
     hipLaunchKernelGGL(k_gen_csr_gt_parts, dim3(n), dim3(TPB), 0, s, g_agg, xs, E > 0 ? row_ptr : nullptr, col, t, eps,
                        lse, M, C, chunk, part);
     if ((rc = gcm_launch_status())) return rc;
-    if ((rc = gt_final(part, n, g_t, s))) return rc;
+    if ((rc = sum_parts(part, n, g_t, s))) return rc;
   }
   return GCM_OK;
 }

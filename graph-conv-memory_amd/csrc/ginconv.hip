@@ -12,6 +12,7 @@
 // epilogue: one launch for h, the same kernel with the adjacency read transposed for g_x.  g_adj is gcn_mm.h's
 // k_gcn_mm as it is.  g_eps: fp64 partial sums of fixed element ranges into the workspace, summed in a fixed order by
 // one workgroup - deterministic, no atomics.  F <= 128; any N.
+#include "fixed_sum.h"
 #include "gcn_mm.h"
 
 namespace {
@@ -21,68 +22,36 @@ template <int NCT>
 __global__ __launch_bounds__(256) void k_gin_mm(const float* __restrict__ adj, const float* __restrict__ X,
                                                 const float* __restrict__ eps, float* __restrict__ C, int N, int F,
                                                 int tr, int add_loop) {
-  constexpr int NC = 32 * NCT;
-  __shared__ float sA[MB * (KT + 1)];  // [i][k]
-  __shared__ float sB[KT * (NC + 1)];  // [k][j]
+  __shared__ float sA[MB * (KT + 1)];        // [i][k]
+  __shared__ float sB[KT * (32 * NCT + 1)];  // [k][j]
   const int b = blockIdx.z;
   const int i0 = blockIdx.x * MB;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  const TileLane t = tile_lane();
   const float* Ab = adj + (size_t)b * N * N;
   const float* Xb = X + (size_t)b * N * F;
   float* Cb = C + (size_t)b * N * F;
-
   f32x16 acc[NCT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-  for (int k0 = 0; k0 < N; k0 += KT) {
-    for (int e = threadIdx.x; e < MB * KT; e += 256) {  // the fast index of the global read is the fast thread index
-      const int r = tr ? e % MB : e / KT, k = tr ? e / MB : e % KT;
-      const int gi = i0 + r, gk = k0 + k;
-      float v = 0.f;
-      if (gi < N && gk < N) v = tr ? Ab[(size_t)gk * N + gi] : Ab[(size_t)gi * N + gk];
-      sA[r * (KT + 1) + k] = v;
-    }
-    for (int e = threadIdx.x; e < KT * NC; e += 256) {
-      const int k = e / NC, j = e % NC;
-      const int gk = k0 + k;
-      sB[k * (NC + 1) + j] = (gk < N && j < F) ? Xb[(size_t)gk * F + j] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-      mma32(acc[c], sA + wave * 32 * (KT + 1), KT + 1, 1, sB + c * 32, NC + 1, 1, KT, li, lh);
-    __syncthreads();
-  }
-
+  tile_zero(acc);
+  tile_mma<NCT, false>(
+      acc, t, sA, sB, i0, 0, N, F, 0, N, tr != 0, false,  // the fast index of the global read is the fast thread index
+      [=](int gi, int gk) { return tr ? Ab[(size_t)gk * N + gi] : Ab[(size_t)gi * N + gk]; },
+      [=](int gk, int gj) { return Xb[(size_t)gk * F + gj]; });
   const float s = add_loop ? 1.f + eps[0] : 0.f;
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int j = c * 32 + li;
-    if (j >= F) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = i0 + wave * 32 + acc_row(r, lh);
-      if (i >= N) continue;
+  tile_store(acc, t, i0, 0, N, F, [=](int j) {
+    return [=](int i, float v) {
       const size_t off = (size_t)i * F + j;
-      float v = acc[c][r];
       if (add_loop) v = fmaf(s, Xb[off], v);
       Cb[off] = v;
-    }
-  }
+    };
+  });
 }
 
 int launch_gin_mm(const float* adj, const float* X, const float* eps, float* C, int B, int N, int F, int tr,
                   int add_loop, hipStream_t s) {
-  const dim3 grid((N + MB - 1) / MB, 1, B);
-  switch ((F + 31) / 32) {
-    case 1: hipLaunchKernelGGL(k_gin_mm<1>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
-    case 2: hipLaunchKernelGGL(k_gin_mm<2>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
-    case 3: hipLaunchKernelGGL(k_gin_mm<3>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
-    default: hipLaunchKernelGGL(k_gin_mm<4>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop); break;
-  }
+  const dim3 grid(blocks(N, MB), 1, B);
+  dispatch_nct(nct_of(F), [&](auto n) {
+    hipLaunchKernelGGL(k_gin_mm<n()>, grid, dim3(256), 0, s, adj, X, eps, C, N, F, tr, add_loop);
+  });
   return gcm_launch_status();
 }
 
@@ -104,7 +73,7 @@ __global__ __launch_bounds__(256) void k_gin_gather(const float* __restrict__ sr
 }
 
 // g_eps, pass 1: part[blk] = sum of a[e] b[e] over the block's element range [blk * chunk, (blk + 1) * chunk), in
-// fp64 (every product exact), lanes and waves combined in a fixed order
+// fp64 (every product exact), lanes and waves combined in a fixed order; pass 2 is fixed_sum.h's sum_parts
 constexpr int DOT_BLOCKS = 1024;  // at most; chunk a multiple of 256
 
 __global__ __launch_bounds__(256) void k_gin_dot_parts(const float* __restrict__ a, const float* __restrict__ b,
@@ -114,28 +83,8 @@ __global__ __launch_bounds__(256) void k_gin_dot_parts(const float* __restrict__
   const int64_t e1 = min(L, e0 + chunk);
   double s = 0.0;
   for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) s += (double)a[e] * (double)b[e];
-  sp[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sp[threadIdx.x] += sp[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = sp[0];
-}
-
-// pass 2 (one workgroup): out[0] = sum of the n partials in a fixed order
-__global__ __launch_bounds__(256) void k_gin_dot_final(const double* __restrict__ part, int n,
-                                                       float* __restrict__ out) {
-  __shared__ double sp[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  sp[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sp[threadIdx.x] += sp[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)sp[0];
+  const double total = block_sum(s, sp);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
 void dot_plan(int64_t L, int* nblocks, int64_t* chunk) {
@@ -158,10 +107,8 @@ int dot_sum(const float* a, const float* b, int64_t L, float* out, void* workspa
   dot_plan(L, &n, &c);
   double* part = (double*)workspace;
   hipLaunchKernelGGL(k_gin_dot_parts, dim3(n), dim3(256), 0, s, a, b, L, c, part);
-  int rc = gcm_launch_status();
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_gin_dot_final, dim3(1), dim3(256), 0, s, part, n, out);
-  return gcm_launch_status();
+  const int rc = gcm_launch_status();
+  return rc ? rc : sum_parts(part, n, out, s);
 }
 
 }  // namespace
@@ -205,8 +152,7 @@ extern "C" int gcm_dense_gin_bwd(const float* g_h, const float* x, const float* 
     if (add_loop) {
       if ((rc = dot_sum(g_h, x, L, g_eps, workspace, s))) return rc;
     } else {  // eps is not used: the sum of no partials
-      hipLaunchKernelGGL(k_gin_dot_final, dim3(1), dim3(256), 0, s, (const double*)workspace, 0, g_eps);
-      if ((rc = gcm_launch_status())) return rc;
+      if ((rc = sum_parts((const double*)workspace, 0, g_eps, s))) return rc;
     }
   }
   return GCM_OK;

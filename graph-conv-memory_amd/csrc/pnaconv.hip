@@ -343,9 +343,8 @@ __global__ __launch_bounds__(256) void k_pna_gx(const float* __restrict__ g_cat,
 }
 
 // ---------------------------------------------------------------------------
-// the input gradients of the linears: gcn_mm.h's tile step (128 rows x 32 NCT columns per workgroup, K in LDS tiles of 32 on
-// v_mfma_f32_32x32x2_f32) with leading dimensions, and every K tile started from a zero accumulator
-// and then added to the running sum (as csrc/tagconv.hip does): the post linear's K is (1 + A S) F_in, up to 3968,
+// the input gradients of the linears: gcn_mm.h's tile step with leading dimensions, and every K tile started from a
+// zero accumulator and then added to the running sum (mma32_tiles): the post linear's K is (1 + A S) F_in, up to 3968,
 // and one fp32 chain of that length over scaled sums misses the tests' bound; with the tiles a chain is 32 products.
 // ---------------------------------------------------------------------------
 struct PmmArgs {
@@ -361,69 +360,28 @@ struct PmmArgs {
 
 template <int NCT>
 __global__ __launch_bounds__(256) void k_pna_mm(PmmArgs p) {
-  constexpr int NC = 32 * NCT;
-  __shared__ float sA[MB * (KT + 1)];  // [i][k]
-  __shared__ float sB[KT * (NC + 1)];  // [k][j]
-  const int i0 = blockIdx.x * MB, j0 = blockIdx.y * NC;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
-  const int kend = p.K;
+  __shared__ float sA[MB * (KT + 1)];        // [i][k]
+  __shared__ float sB[KT * (32 * NCT + 1)];  // [k][j]
+  const int i0 = blockIdx.x * MB, j0 = blockIdx.y * 32 * NCT;
+  const TileLane t = tile_lane();
   const bool a_rfast = p.a_is == 1 && p.a_ks != 1;  // coalesced order of the global reads
   const bool b_kfast = p.b_ks == 1 && p.b_js != 1;
-
   f32x16 acc[NCT];
-#pragma unroll
-  for (int c = 0; c < NCT; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-  for (int k0 = 0; k0 < kend; k0 += KT) {
-    for (int e = threadIdx.x; e < MB * KT; e += 256) {
-      const int r = a_rfast ? e % MB : e / KT, k = a_rfast ? e / MB : e % KT;
-      const int gi = i0 + r, gk = k0 + k;
-      sA[r * (KT + 1) + k] = (gi < p.M && gk < kend) ? p.A[(size_t)gi * p.a_is + (size_t)gk * p.a_ks] : 0.f;
-    }
-    for (int e = threadIdx.x; e < KT * NC; e += 256) {
-      const int k = b_kfast ? e % KT : e / NC, j = b_kfast ? e / KT : e % NC;
-      const int gk = k0 + k, gj = j0 + j;
-      sB[k * (NC + 1) + j] = (gk < kend && gj < p.N) ? p.B[(size_t)gk * p.b_ks + (size_t)gj * p.b_js] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCT; ++c) {
-      f32x16 tile;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tile[r] = 0.f;
-      mma32(tile, sA + wave * 32 * (KT + 1), KT + 1, 1, sB + c * 32, NC + 1, 1, KT, li, lh);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][r] += tile[r];
-    }
-    __syncthreads();
-  }
-
-  float* Cs = p.C;
-#pragma unroll
-  for (int c = 0; c < NCT; ++c) {
-    const int j = j0 + c * 32 + li;
-    if (j >= p.N) continue;
+  tile_zero(acc);
+  tile_mma<NCT, true>(
+      acc, t, sA, sB, i0, j0, p.M, p.N, 0, p.K, a_rfast, b_kfast,
+      [=](int gi, int gk) { return p.A[(size_t)gi * p.a_is + (size_t)gk * p.a_ks]; },
+      [=](int gk, int gj) { return p.B[(size_t)gk * p.b_ks + (size_t)gj * p.b_js]; });
+  tile_store(acc, t, i0, j0, p.M, p.N, [=](int j) {
     const float bias = p.bias ? p.bias[j] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = i0 + wave * 32 + acc_row(r, lh);
-      if (i < p.M) Cs[(size_t)i * p.c_is + j] = acc[c][r] + bias;
-    }
-  }
+    return [=](int i, float v) { p.C[(size_t)i * p.c_is + j] = v + bias; };
+  });
 }
 
 int launch_pmm(const PmmArgs& p, hipStream_t s) {
-  const int nct = p.N > 96 ? 4 : (p.N > 64 ? 3 : (p.N > 32 ? 2 : 1));
-  const int NC = 32 * nct;
-  const dim3 grid((p.M + MB - 1) / MB, (p.N + NC - 1) / NC);
-  switch (nct) {
-    case 1: hipLaunchKernelGGL(k_pna_mm<1>, grid, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(k_pna_mm<2>, grid, dim3(256), 0, s, p); break;
-    case 3: hipLaunchKernelGGL(k_pna_mm<3>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(k_pna_mm<4>, grid, dim3(256), 0, s, p); break;
-  }
+  const int nct = nct_of(p.N);
+  const dim3 grid(blocks(p.M, MB), blocks(p.N, 32 * nct));
+  dispatch_nct(nct, [&](auto n) { hipLaunchKernelGGL(k_pna_mm<n()>, grid, dim3(256), 0, s, p); });
   return gcm_launch_status();
 }
 
@@ -449,11 +407,8 @@ __global__ __launch_bounds__(256) void k_pna_mm64(PmmArgs p) {
     for (int u = 0; u < CC; ++u) acc[q][u] = 0.0;
 
   for (int k0 = 0; k0 < p.K; k0 += KT) {
-    for (int e = threadIdx.x; e < MB * KT; e += 256) {
-      const int rr = a_rfast ? e % MB : e / KT, k = a_rfast ? e / MB : e % KT;
-      const int gi = i0 + rr, gk = k0 + k;
-      sA[rr * (KT + 1) + k] = (gi < p.M && gk < p.K) ? p.A[(size_t)gi * p.a_is + (size_t)gk * p.a_ks] : 0.f;
-    }
+    tile_stage_a(sA, i0, p.M, k0, p.K, a_rfast,
+                 [=](int gi, int gk) { return p.A[(size_t)gi * p.a_is + (size_t)gk * p.a_ks]; });
     for (int e = threadIdx.x; e < KT * NC; e += 256) {
       const int k = b_kfast ? e % KT : e / NC, j = b_kfast ? e / KT : e % NC;
       const int gk = k0 + k, gj = j0 + j;
@@ -489,15 +444,9 @@ __global__ __launch_bounds__(256) void k_pna_mm64(PmmArgs p) {
 }
 
 int launch_pmm64(const PmmArgs& p, hipStream_t s) {
-  const int nct = p.N > 96 ? 4 : (p.N > 64 ? 3 : (p.N > 32 ? 2 : 1));
-  const int NC = 32 * nct;
-  const dim3 grid((p.M + MB - 1) / MB, (p.N + NC - 1) / NC);
-  switch (nct) {
-    case 1: hipLaunchKernelGGL(k_pna_mm64<1>, grid, dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(k_pna_mm64<2>, grid, dim3(256), 0, s, p); break;
-    case 3: hipLaunchKernelGGL(k_pna_mm64<3>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(k_pna_mm64<4>, grid, dim3(256), 0, s, p); break;
-  }
+  const int nct = nct_of(p.N);
+  const dim3 grid(blocks(p.M, MB), blocks(p.N, 32 * nct));
+  dispatch_nct(nct, [&](auto n) { hipLaunchKernelGGL(k_pna_mm64<n()>, grid, dim3(256), 0, s, p); });
   return gcm_launch_status();
 }
 

@@ -490,8 +490,7 @@ extern "C" int gcm_dense_resgatedconv_fwd(const float* x, const float* adj, cons
   char* sv = (char*)saved;
   unsigned* bits = (unsigned*)(sv + L.bits);
   float* proj = (float*)(sv + L.proj);
-  hipLaunchKernelGGL(k_gat_mask_bits, dim3(blocks(R, 4)), dim3(256), 0, s, adj, bits, R, N, W, add_loop);
-  int rc = gcm_launch_status();
+  int rc = mask_bits(adj, bits, R, N, W, add_loop, s);
   if (rc || (rc = project(x, w_all, b_all, proj, d, s))) return rc;
   RG_LAUNCH(k_rg_dense_fwd, RG_DENSE_GRID, s, (const unsigned*)bits, adj, (const float*)proj, d.P, bias, out, N, C,
             root, add_loop)
@@ -531,8 +530,7 @@ extern "C" int gcm_dense_resgatedconv_bwd(const float* g_out, const float* x, co
   }
   if (g_x || g_w_all || g_b_all) {
     unsigned* bitsT = (unsigned*)(ws + K.bitsT);
-    hipLaunchKernelGGL(k_mask_bits_t, dim3(blocks(R * W, 256)), dim3(256), 0, s, bits, bitsT, R, N, W);
-    if ((rc = gcm_launch_status())) return rc;
+    if ((rc = mask_bits_t(bits, bitsT, R, N, W, s))) return rc;
     RG_LAUNCH(k_rg_dense_dcol, RG_DENSE_GRID, s, (const unsigned*)bitsT, adj, proj, d.P, g_out, gp, N, C, add_loop)
     if ((rc = gcm_launch_status())) return rc;
   }

@@ -24,20 +24,6 @@ namespace {
 
 __device__ __forceinline__ float tag_dinv(float deg) { return deg == 0.f ? 0.f : 1.f / sqrtf(deg); }
 
-// acc += A(32 x KK) B(KK x 32), operands in LDS as mma32's, in K tiles of 32 that each start from a zero accumulator:
-// no fp32 chain is longer than 32 products before it meets the running sum (one chain over every hop and channel of
-// `out` - 320 products at K = 4, 64 channels - missed the tests' bound: 3.1e-6 against 2.4e-6)
-__device__ __forceinline__ void mma32_tiles(f32x16& acc, const float* a, int ais, int aks, const float* b, int bks,
-                                            int bjs, int KK, int li, int lh) {
-  for (int k0 = 0; k0 < KK; k0 += 32) {
-    f32x16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.f;
-    mma32(t, a + k0 * aks, ais, aks, b + k0 * bks, bks, bjs, 32, li, lh);
-    acc += t;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // dense, N <= 128: the LDS image of A^ shared by the forward and the chain
 // ---------------------------------------------------------------------------
@@ -803,12 +789,10 @@ extern "C" int gcm_csr_tagconv_fwd(const float* x, const int64_t* row_ptr, const
     const float* w0 = k <= 1 ? weight : nullptr;
     const float* wk = k == 0 ? nullptr : weight + (size_t)k * wsz;
     float* hnext = k == 0 ? nullptr : hs + (size_t)(k - 1) * hop;
-    switch ((Fi + 31) / 32) {
-      case 1: hipLaunchKernelGGL(k_tag_csr_hop<1>, grid, dim3(256), 0, s, hprev, row_ptr, col, coef, w0, bias, wk, out, hnext, M, Fi, Fo); break;
-      case 2: hipLaunchKernelGGL(k_tag_csr_hop<2>, grid, dim3(256), 0, s, hprev, row_ptr, col, coef, w0, bias, wk, out, hnext, M, Fi, Fo); break;
-      case 3: hipLaunchKernelGGL(k_tag_csr_hop<3>, grid, dim3(256), 0, s, hprev, row_ptr, col, coef, w0, bias, wk, out, hnext, M, Fi, Fo); break;
-      default: hipLaunchKernelGGL(k_tag_csr_hop<4>, grid, dim3(256), 0, s, hprev, row_ptr, col, coef, w0, bias, wk, out, hnext, M, Fi, Fo); break;
-    }
+    dispatch_nct((Fi + 31) / 32, [&](auto n) {
+      hipLaunchKernelGGL(k_tag_csr_hop<n()>, grid, dim3(256), 0, s, hprev, row_ptr, col, coef, w0, bias, wk, out, hnext,
+                         M, Fi, Fo);
+    });
     const int rc = gcm_launch_status();
     if (rc) return rc;
   }

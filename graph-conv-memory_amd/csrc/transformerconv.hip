@@ -635,15 +635,6 @@ int bwd_tail(const float* x, const float* w_all, float* g_x, float* g_w_all, flo
 
 int dense_blocks(int N) { return (N + 127) / 128; }
 
-// launch K<NCTC> for the C of this layer
-#define TR_LAUNCH_NCTC(K, grid, s, ...)                                                   \
-  switch ((C + 31) / 32) {                                                                \
-    case 1: hipLaunchKernelGGL(K<1>, grid, dim3(256), 0, s, __VA_ARGS__); break;          \
-    case 2: hipLaunchKernelGGL(K<2>, grid, dim3(256), 0, s, __VA_ARGS__); break;          \
-    case 3: hipLaunchKernelGGL(K<3>, grid, dim3(256), 0, s, __VA_ARGS__); break;          \
-    default: hipLaunchKernelGGL(K<4>, grid, dim3(256), 0, s, __VA_ARGS__); break;         \
-  }
-
 // launch K<G> with the lane group of this C: n groups
 #define TR_LAUNCH_GROUP(K, n, s, ...)                                                                       \
   if (C <= 8) hipLaunchKernelGGL(K<8>, dim3(blocks((n) * 8, 256)), dim3(256), 0, s, __VA_ARGS__);           \
@@ -680,13 +671,14 @@ extern "C" int gcm_dense_transformerconv_fwd(const float* x, const float* adj, c
   char* sv = (char*)saved;
   unsigned* bits = (unsigned*)(sv + L.bits);
   float* proj = (float*)(sv + L.proj);
-  hipLaunchKernelGGL(k_gat_mask_bits, dim3(blocks(R, 4)), dim3(256), 0, s, adj, bits, R, N, W, add_loop);
-  int rc = gcm_launch_status();
+  int rc = mask_bits(adj, bits, R, N, W, add_loop, s);
   if (rc || (rc = project(x, w_all, b_all, proj, d, s))) return rc;
   const dim3 grid(dense_blocks(N), B);
   const float scale = 1.f / sqrtf((float)C);
-  TR_LAUNCH_NCTC(k_tr_dense_fwd, grid, s, bits, proj, d.P, (float*)(sv + L.o), (float*)(sv + L.m), (float*)(sv + L.l),
-                 N, H, C, scale)
+  dispatch_nct((C + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_tr_dense_fwd<n()>, grid, dim3(256), 0, s, bits, proj, d.P, (float*)(sv + L.o),
+                       (float*)(sv + L.m), (float*)(sv + L.l), N, H, C, scale);
+  });
   if ((rc = gcm_launch_status())) return rc;
   return fwd_tail(w_beta, out, L, sv, d, concat, s);
 }
@@ -727,9 +719,15 @@ extern "C" int gcm_dense_transformerconv_bwd(const float* g_out, const float* x,
   float* gp = (float*)(ws + K.gp);
   const dim3 grid(dense_blocks(N), B);
   const float scale = 1.f / sqrtf((float)C);
-  TR_LAUNCH_NCTC(k_tr_dense_dq, grid, s, bits, proj, d.P, dO, row_m, row_l, delta, gp, N, H, C, scale)
+  dispatch_nct((C + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_tr_dense_dq<n()>, grid, dim3(256), 0, s, bits, proj, d.P, dO, row_m, row_l, delta, gp, N, H, C,
+                       scale);
+  });
   if ((rc = gcm_launch_status())) return rc;
-  TR_LAUNCH_NCTC(k_tr_dense_dkv, grid, s, bits, proj, d.P, dO, row_m, row_l, (const float*)delta, gp, N, H, C, scale)
+  dispatch_nct((C + 31) / 32, [&](auto n) {
+    hipLaunchKernelGGL(k_tr_dense_dkv<n()>, grid, dim3(256), 0, s, bits, proj, d.P, dO, row_m, row_l,
+                       (const float*)delta, gp, N, H, C, scale);
+  });
   if ((rc = gcm_launch_status())) return rc;
   return bwd_tail(x, w_all, g_x, g_w_all, g_b_all, K, ws, d, s);
 }
