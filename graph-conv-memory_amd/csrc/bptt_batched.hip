@@ -371,10 +371,6 @@ int launch_bptt(hipStream_t s, int grid, const float* g_mx, const float* g_no, c
 
 }  // namespace gcm_fused
 
-#define GCM_BSHAPES_N(X, a) \
-  X(a, 1, 1, 1) X(a, 1, 1, 2) X(a, 1, 2, 1) X(a, 1, 2, 2) X(a, 2, 1, 1) X(a, 2, 1, 2) X(a, 2, 2, 1) X(a, 2, 2, 2)
-#define GCM_BSHAPES(X) GCM_BSHAPES_N(X, 1) GCM_BSHAPES_N(X, 2) GCM_BSHAPES_N(X, 3) GCM_BSHAPES_N(X, 4)
-
 extern "C" int gcm_dense_bptt_batched_slabs(int items) {
   // persistent grid: enough workgroups for 3 per CU; one parameter-gradient slab each
   static int cus = 0;
@@ -406,13 +402,9 @@ extern "C" int gcm_dense_bptt_batched(const float* g_mx, const float* g_nodes_ou
     return GCM_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   gcm_fused::Gnn2 P{w_rel1, b_rel1, w_root1, w_rel2, b_rel2, w_root2, act1, act2};
-  const int NT = N / 32, NCT = F / 32, NHT = H1 / 32, N2T = H2 / 32;
-#define GCM_B(a, b_, c, d)                                                                      \
-  if (NT == a && NCT == b_ && NHT == c && N2T == d)                                             \
-    return gcm_fused::launch_bptt<a, b_, c, d>(s, n_slabs, g_mx, g_nodes_out, x, adj, cur_idx,  \
-                                               num_nodes_in, P, mx, h1, agg1, agg2, Q, pobs,    \
-                                               slabs, items);
-  GCM_BSHAPES(GCM_B)
-#undef GCM_B
-  return GCM_EUNSUPPORTED;
+  return gcm_fused::pick_shape(N, F, H1, H2, [&](auto nt, auto nct, auto nht, auto n2t) {   // exact shapes only
+    return gcm_fused::launch_bptt<nt(), nct(), nht(), n2t()>(s, n_slabs, g_mx, g_nodes_out, x, adj, cur_idx,
+                                                             num_nodes_in, P, mx, h1, agg1, agg2, Q, pobs, slabs,
+                                                             items);
+  });
 }

@@ -1094,32 +1094,28 @@ static int run_distance(const View& vw, float* adj, float* sel_row, int mode, fl
       const int CBv = FT >= 4 ? 128 : 256;   // (fits 160 KB of LDS)
       const size_t lds = sizeof(float) * ((size_t)RB * (32 * FT + 1) + (size_t)32 * FT * (CBv + 1) + RB + CBv +
                                           (size_t)(8 / (RB / 32) - 1) * RB);
-#define GCM_EUCLID_MFMA(FTv)                                                                     \
-  {                                                                                              \
-    auto kern = k_euclid_mfma<FTv, RB, (FTv >= 4 ? 128 : 256)>;                                  \
-    gcm_allow_dynamic_lds((const void*)kern, lds);                                               \
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, vw, dist_param, adj, sel_row, dist_out,    \
-                       max_distance, bidirectional, Bc, N, F);                                   \
-  }
       // F <= 64: tiles dealt by liveness, double-buffered chunks of 128 graphs (k_euclid_mfma2)
       const size_t lds2 = sizeof(float) * ((size_t)RB * (32 * FT + 1) + (size_t)2 * 32 * FT * 129 + RB + 2 * 128 +
                                            (size_t)8 * RB);
-#define GCM_EUCLID_MFMA2(FTv)                                                                    \
-  {                                                                                              \
-    auto kern = k_euclid_mfma2<FTv, 0>;                                                          \
-    gcm_allow_dynamic_lds((const void*)kern, lds2);                                              \
-    hipLaunchKernelGGL(kern, grid, dim3(1024), lds2, s, vw, dist_param, adj, sel_row, dist_out,  \
-                       max_distance, bidirectional, Bc, N, F, StepTail{});                       \
-  }
-      switch (FT) {
-        case 1: GCM_EUCLID_MFMA2(1) break;
-        case 2: GCM_EUCLID_MFMA2(2) break;
-        case 3: GCM_EUCLID_MFMA(3) break;
-        default: GCM_EUCLID_MFMA(4) break;
-      }
-#undef GCM_EUCLID_MFMA2
-#undef GCM_EUCLID_MFMA
-      return gcm_launch_status();
+      if (FT == 1 || FT == 2)
+        return gcm_pick(
+            [&](auto ft) {
+              auto kern = k_euclid_mfma2<ft(), 0>;
+              gcm_allow_dynamic_lds((const void*)kern, lds2);
+              hipLaunchKernelGGL(kern, grid, dim3(1024), lds2, s, vw, dist_param, adj, sel_row, dist_out, max_distance,
+                                 bidirectional, Bc, N, F, StepTail{});
+              return gcm_launch_status();
+            },
+            OneOf<1, 2>{FT});
+      return gcm_pick(
+          [&](auto ft) {
+            auto kern = k_euclid_mfma<ft(), RB, (ft() >= 4 ? 128 : 256)>;
+            gcm_allow_dynamic_lds((const void*)kern, lds);
+            hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, vw, dist_param, adj, sel_row, dist_out, max_distance,
+                               bidirectional, Bc, N, F);
+            return gcm_launch_status();
+          },
+          OneOf<3, 4>{FT == 3 ? 3 : 4});
     }
     GCM_REQUIRE(workspace);
     if (workspace_bytes < ((size_t)Bc * F + Bc) * sizeof(float)) return GCM_EWORKSPACE;
@@ -1127,15 +1123,13 @@ static int run_distance(const View& vw, float* adj, float* sel_row, int mode, fl
     hipLaunchKernelGGL(k_gather_cur, dim3((Bc * F + 255) / 256), dim3(256), 0, s, vw, dist_param, ws_cur,
                        Bc, N, F);
     dim3 grid((N + 127) / 128, B);
-#define GCM_EUCLID(FP)                                                                        \
-  hipLaunchKernelGGL(k_euclid_crossbatch<FP>, grid, dim3(128), 0, s, vw, ws_cur, dist_param, adj, \
-                     sel_row, dist_out, max_distance, bidirectional, Bc, N, F)
-    if (F <= 16) GCM_EUCLID(16);
-    else if (F <= 32) GCM_EUCLID(32);
-    else if (F <= 64) GCM_EUCLID(64);
-    else GCM_EUCLID(128);
-#undef GCM_EUCLID
-    return gcm_launch_status();
+    return gcm_pick(
+        [&](auto fp) {
+          hipLaunchKernelGGL(k_euclid_crossbatch<fp()>, grid, dim3(128), 0, s, vw, ws_cur, dist_param, adj, sel_row,
+                             dist_out, max_distance, bidirectional, Bc, N, F);
+          return gcm_launch_status();
+        },
+        OneOf<16, 32, 64, 128>{F <= 16 ? 16 : F <= 32 ? 32 : F <= 64 ? 64 : 128});
   }
   if (mode == GCM_DIST_L2_PERGRAPH) {
     GCM_REQUIRE(a0 >= 0 && a1 > a0 && a1 <= F && b0 >= 0 && b1 <= F && (b1 - b0) == (a1 - a0));

@@ -476,20 +476,13 @@ int launch_fwd(const float* P, const float* Q, const float* adj, const int64_t* 
   // DenseEdge pattern with 8 rows a wave)
   const int RW = CSR ? 16 : 2;
   const dim3 grid(grid_of(rows, (int64_t)WPB * RW), (C + 63) / 64);
-#define GCM_EDGEMAX_FWD(CW, HMAX)                                                                               \
-  hipLaunchKernelGGL((k_edgemax_fwd<CW, HMAX, CSR>), grid, dim3(TPB), 0, s, P, Q, adj, row_ptr, col, w2, b2, slope, \
-                     out, winner, rows, N, H, C, RW)
-  if (H <= 32) {
-    if (C <= 16) GCM_EDGEMAX_FWD(16, 32);
-    else if (C <= 32) GCM_EDGEMAX_FWD(32, 32);
-    else GCM_EDGEMAX_FWD(64, 32);
-  } else {
-    if (C <= 16) GCM_EDGEMAX_FWD(16, 128);
-    else if (C <= 32) GCM_EDGEMAX_FWD(32, 128);
-    else GCM_EDGEMAX_FWD(64, 128);
-  }
-#undef GCM_EDGEMAX_FWD
-  return gcm_launch_status();
+  return gcm_pick(
+      [&](auto cw, auto hmax) {
+        hipLaunchKernelGGL((k_edgemax_fwd<cw(), hmax(), CSR>), grid, dim3(TPB), 0, s, P, Q, adj, row_ptr, col, w2, b2,
+                           slope, out, winner, rows, N, H, C, RW);
+        return gcm_launch_status();
+      },
+      OneOf<16, 32, 64>{C <= 16 ? 16 : C <= 32 ? 32 : 64}, OneOf<32, 128>{H <= 32 ? 32 : 128});
 }
 
 template <bool CSR>

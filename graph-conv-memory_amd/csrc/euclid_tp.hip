@@ -482,16 +482,14 @@ extern "C" int gcm_euclid_rollout_tp_decide(const float* obs, float max_distance
   const int FT = (F + 31) / 32, FP = 32 * FT;
   const size_t lds = sizeof(float) * ((size_t)128 * (FP + 1) + (size_t)3 * FP * 129 + 128 + 3 * 128 + (size_t)4 * 8 * 128);
   hipStream_t s = (hipStream_t)stream;
-  if (FT == 1) {
-    auto kern = gcm_etp::k_euclid_tp<1>;
-    gcm_allow_dynamic_lds((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, s, obs, dist_param, max_distance, decbits, T, B, N, F);
-  } else {
-    auto kern = gcm_etp::k_euclid_tp<2>;
-    gcm_allow_dynamic_lds((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, s, obs, dist_param, max_distance, decbits, T, B, N, F);
-  }
-  return gcm_launch_status();
+  return gcm_pick(
+      [&](auto ft) {
+        auto kern = gcm_etp::k_euclid_tp<ft()>;
+        gcm_allow_dynamic_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, dim3(B), dim3(1024), lds, s, obs, dist_param, max_distance, decbits, T, B, N, F);
+        return gcm_launch_status();
+      },
+      OneOf<1, 2>{FT == 1 ? 1 : 2});
 }
 
 extern "C" int gcm_euclid_rollout_tp_fwd(const float* obs, float max_distance, const float* dist_param,
@@ -509,18 +507,17 @@ extern "C" int gcm_euclid_rollout_tp_fwd(const float* obs, float max_distance, c
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int FP = F <= 32 ? 32 : 64, HP = H1 <= 32 ? 32 : 64;
-#define GCM_ETP_GNN(a, b_)                                                                                          \
-  if (FP == a && HP == b_) {                                                                                        \
-    auto k2 = gcm_etp::k_euclid_tp_gnn<a, b_>;                                                                      \
-    const size_t lds2 = sizeof(float) * ((size_t)128 * (a + 1) + (size_t)128 * ((a > b_ ? a : b_) + 1) +              \
-                                         (size_t)128 * (b_ + 1) +                                                   \
-                                         (2 * a * (b_ + 1) > 2 * b_ * 65 ? (size_t)2 * a * (b_ + 1) : (size_t)2 * b_ * 65) + 128 * 4);                                          \
-    gcm_allow_dynamic_lds((const void*)k2, lds2);                                                                   \
-    hipLaunchKernelGGL(k2, dim3(B), dim3(256), lds2, s, obs, decbits, params, act1, act2, cache_h1, cache_agg1,     \
-                       cache_nodes, nodes, adj, count, mx_all, records, rec_stride, lay, record, flags, T, B, N, Tc, \
-                       F, H1, H2);                                                                                  \
-  }
-  GCM_ETP_GNN(32, 32) GCM_ETP_GNN(64, 32) GCM_ETP_GNN(32, 64) GCM_ETP_GNN(64, 64)
-#undef GCM_ETP_GNN
-  return gcm_launch_status();
+  return gcm_pick(
+      [&](auto fp, auto hp) {
+        constexpr size_t a = fp(), b = hp();
+        auto k2 = gcm_etp::k_euclid_tp_gnn<fp(), hp()>;
+        const size_t lds2 = sizeof(float) * (128 * (a + 1) + 128 * ((a > b ? a : b) + 1) + 128 * (b + 1) +
+                                             (2 * a * (b + 1) > 2 * b * 65 ? 2 * a * (b + 1) : 2 * b * 65) + 128 * 4);
+        gcm_allow_dynamic_lds((const void*)k2, lds2);
+        hipLaunchKernelGGL(k2, dim3(B), dim3(256), lds2, s, obs, decbits, params, act1, act2, cache_h1, cache_agg1,
+                           cache_nodes, nodes, adj, count, mx_all, records, rec_stride, lay, record, flags, T, B, N, Tc,
+                           F, H1, H2);
+        return gcm_launch_status();
+      },
+      OneOf<32, 64>{FP}, OneOf<32, 64>{HP});
 }

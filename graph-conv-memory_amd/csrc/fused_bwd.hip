@@ -390,15 +390,11 @@ extern "C" int gcm_dense_gnn2_row_bwd(const float* g_mx, const float* g_nodes_ou
   if (!gcm_dense_gnn2_row_supported(N, F, H1, H2)) return GCM_EUNSUPPORTED;
   gcm_fused::Gnn2 P{w_rel1, b_rel1, w_root1, w_rel2, b_rel2, w_root2, act1, act2};
   hipStream_t s = (hipStream_t)stream;
-  const int NT = (N + 31) / 32, NCT = (F + 31) / 32, NHT = (H1 + 31) / 32, N2T = (H2 + 31) / 32;
-#define GCM_B(a, b_, c, d)                                                                     \
-  if (NT == a && NCT == b_ && NHT == c && N2T == d)                                            \
-    return gcm_fused::launch_bwd<a, b_, c, d>(s, g_mx, g_nodes_out, x, adj, cur_idx,           \
-                                              num_nodes_in, P, mx, h1, agg1, agg2, g_nodes_in, \
-                                              g_obs, slabs, accumulate, B, N, F, H1, H2);
-  GCM_SHAPES(GCM_B)
-#undef GCM_B
-  return GCM_EUNSUPPORTED;
+  return gcm_fused::pick_shape(N, F, H1, H2, [&](auto nt, auto nct, auto nht, auto n2t) {
+    return gcm_fused::launch_bwd<nt(), nct(), nht(), n2t()>(s, g_mx, g_nodes_out, x, adj, cur_idx, num_nodes_in, P, mx,
+                                                            h1, agg1, agg2, g_nodes_in, g_obs, slabs, accumulate, B, N,
+                                                            F, H1, H2);
+  });
 }
 
 extern "C" int gcm_sum_slabs(const float* slabs, int n_slabs, int len, float* out,

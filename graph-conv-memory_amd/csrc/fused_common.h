@@ -335,9 +335,12 @@ inline void lds_need(int NT, int NCT, int NHT, int N2T, size_t* fwd, size_t* bwd
   *bwd = sizeof(float) * (ADJ + NP * HS + NP * FS + 2 * HP * FS + W2 + 4 * 1024 + SV);
 }
 
-}  // namespace gcm_fused
+// the instantiated shapes (NT, NCT, NHT, N2T) of N <= 128, F, H1, H2 <= 64: f(nt, nct, nht, n2t) as gcm_pick calls it.
+// Stated once, so forward, backward and the rollouts dispatch identically.
+template <typename Fn>
+int pick_shape(int N, int F, int H1, int H2, Fn f) {
+  return gcm_pick(f, OneOf<1, 2, 3, 4>{(N + 31) / 32}, OneOf<1, 2>{(F + 31) / 32}, OneOf<1, 2>{(H1 + 31) / 32},
+                  OneOf<1, 2>{(H2 + 31) / 32});
+}
 
-// instantiated shapes (NT, NCT, NHT, N2T); one X-macro keeps forward and backward dispatch identical
-#define GCM_SHAPES_N(X, a) \
-  X(a, 1, 1, 1) X(a, 1, 1, 2) X(a, 1, 2, 1) X(a, 1, 2, 2) X(a, 2, 1, 1) X(a, 2, 1, 2) X(a, 2, 2, 1) X(a, 2, 2, 2)
-#define GCM_SHAPES(X) GCM_SHAPES_N(X, 1) GCM_SHAPES_N(X, 2) GCM_SHAPES_N(X, 3) GCM_SHAPES_N(X, 4)
+}  // namespace gcm_fused

@@ -452,14 +452,10 @@ extern "C" int gcm_dense_gnn2_row_fwd(const float* x, const float* adj, const in
   if (!gcm_dense_gnn2_row_supported(N, F, H1, H2)) return GCM_EUNSUPPORTED;
   gcm_fused::Gnn2 P{w_rel1, b_rel1, w_root1, w_rel2, b_rel2, w_root2, act1, act2};
   hipStream_t s = (hipStream_t)stream;
-  const int NT = (N + 31) / 32, NCT = (F + 31) / 32, NHT = (H1 + 31) / 32, N2T = (H2 + 31) / 32;
-#define GCM_F(a, b_, c, d)                                                                   \
-  if (NT == a && NCT == b_ && NHT == c && N2T == d)                                          \
-    return gcm_fused::launch_fwd<a, b_, c, d>(s, x, adj, cur_idx, P, mx, h1, agg1, agg2,     \
-                                              flags, B, N, F, H1, H2);
-  GCM_SHAPES(GCM_F)
-#undef GCM_F
-  return GCM_EUNSUPPORTED;
+  return gcm_fused::pick_shape(N, F, H1, H2, [&](auto nt, auto nct, auto nht, auto n2t) {
+    return gcm_fused::launch_fwd<nt(), nct(), nht(), n2t()>(s, x, adj, cur_idx, P, mx, h1, agg1, agg2, flags, B, N, F,
+                                                            H1, H2);
+  });
 }
 
 /* One kernel per forward step: state advance (gcm.py:262-278, 323-355) + temporal/dense selector
@@ -499,12 +495,8 @@ extern "C" int gcm_dense_step_fused_fwd(const float* obs, const float* nodes_in,
   }
   gcm_fused::Gnn2 P{w_rel1, b_rel1, w_root1, w_rel2, b_rel2, w_root2, act1, act2};
   hipStream_t s = (hipStream_t)stream;
-  const int NT = (N + 31) / 32, NCT = (F + 31) / 32, NHT = (H1 + 31) / 32, N2T = (H2 + 31) / 32;
-#define GCM_S(a, b_, c, d)                                                                    \
-  if (NT == a && NCT == b_ && NHT == c && N2T == d)                                           \
-    return gcm_fused::launch_step<a, b_, c, d>(s, nodes_in, adj_in, A, P, mx, h1, agg1, agg2, \
-                                               flags, B, N, F, H1, H2);
-  GCM_SHAPES(GCM_S)
-#undef GCM_S
-  return GCM_EUNSUPPORTED;
+  return gcm_fused::pick_shape(N, F, H1, H2, [&](auto nt, auto nct, auto nht, auto n2t) {
+    return gcm_fused::launch_step<nt(), nct(), nht(), n2t()>(s, nodes_in, adj_in, A, P, mx, h1, agg1, agg2, flags, B, N,
+                                                             F, H1, H2);
+  });
 }

@@ -328,8 +328,11 @@ int launch_layer_bwd(hipStream_t s, const float* g_out, const float* out, const 
 
 }  // namespace gcm_fused
 
-#define GCM_LSHAPES_N(X, a) X(a, 1, 1) X(a, 1, 2) X(a, 2, 1) X(a, 2, 2)
-#define GCM_LSHAPES(X) GCM_LSHAPES_N(X, 1) GCM_LSHAPES_N(X, 2) GCM_LSHAPES_N(X, 3) GCM_LSHAPES_N(X, 4)
+// the instantiated shapes (NT, NCT, NHT) of a layer with N <= 128, Fi, Fo <= 64
+template <typename Fn>
+static int pick_layer_shape(int N, int Fi, int Fo, Fn f) {
+  return gcm_pick(f, OneOf<1, 2, 3, 4>{(N + 31) / 32}, OneOf<1, 2>{(Fi + 31) / 32}, OneOf<1, 2>{(Fo + 31) / 32});
+}
 
 // internal entry points used by graphconv.hip's C ABI when the graph fits one workgroup
 // which = 0: forward kernel, 1: backward without g_adj, 2: backward with g_adj
@@ -343,24 +346,18 @@ int gcm_layer_fits(int N, int Fi, int Fo, int which) {
 int gcm_layer_fwd(const float* x, const float* adj, const float* w_rel, const float* b_rel,
                   const float* w_root, float* out, float* agg, int B, int N, int Fi, int Fo,
                   int act, hipStream_t s) {
-  const int NT = (N + 31) / 32, NCT = (Fi + 31) / 32, NHT = (Fo + 31) / 32;
-#define GCM_LF(a, b_, c)                      \
-  if (NT == a && NCT == b_ && NHT == c)       \
-    return gcm_fused::launch_layer_fwd<a, b_, c>(s, x, adj, w_rel, b_rel, w_root, out, agg, B, N, Fi, Fo, act);
-  GCM_LSHAPES(GCM_LF)
-#undef GCM_LF
-  return GCM_EUNSUPPORTED;
+  return pick_layer_shape(N, Fi, Fo, [&](auto nt, auto nct, auto nht) {
+    return gcm_fused::launch_layer_fwd<nt(), nct(), nht()>(s, x, adj, w_rel, b_rel, w_root, out, agg, B, N, Fi, Fo,
+                                                           act);
+  });
 }
 
 int gcm_layer_bwd(const float* g_out, const float* out, const float* x, const float* adj,
                   const float* agg, const float* w_rel, const float* w_root, float* g_x,
                   float* g_adj, float* slabs, int want_w, int B, int N, int Fi, int Fo, int act,
                   hipStream_t s) {
-  const int NT = (N + 31) / 32, NCT = (Fi + 31) / 32, NHT = (Fo + 31) / 32;
-#define GCM_LB(a, b_, c)                      \
-  if (NT == a && NCT == b_ && NHT == c)       \
-    return gcm_fused::launch_layer_bwd<a, b_, c>(s, g_out, out, x, adj, agg, w_rel, w_root, g_x, g_adj, slabs, want_w, B, N, Fi, Fo, act);
-  GCM_LSHAPES(GCM_LB)
-#undef GCM_LB
-  return GCM_EUNSUPPORTED;
+  return pick_layer_shape(N, Fi, Fo, [&](auto nt, auto nct, auto nht) {
+    return gcm_fused::launch_layer_bwd<nt(), nct(), nht()>(s, g_out, out, x, adj, agg, w_rel, w_root, g_x, g_adj, slabs,
+                                                           want_w, B, N, Fi, Fo, act);
+  });
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gcm_dispatch.h"
 #include "gcm_hip.h"
 
 #define GCM_REQUIRE(cond) \

@@ -130,12 +130,12 @@ inline int nct_of(int n) { return std::clamp((n + 31) / 32, 1, 4); }
 // f(std::integral_constant<int, NCT>) for NCT = min(nct, 4): the launch of a kernel's <1>..<4> instantiation
 template <typename F>
 void dispatch_nct(int nct, F f) {
-  switch (nct) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    default: f(std::integral_constant<int, 4>{}); break;
-  }
+  gcm_pick(
+      [&](auto n) {
+        f(n);
+        return GCM_OK;
+      },
+      OneOf<1, 2, 3, 4>{nct >= 1 && nct <= 3 ? nct : 4});
 }
 
 // C(b, i, j) = epi( sum_k A(b, i, k) * B(b, k, j) ),   k in [kbeg, kend) of split z

@@ -31,6 +31,7 @@ __host__ __device__ constexpr int round32(int v) { return (v + 31) & ~31; }
 // acc(32x32) += A(32 x K) * B(K x 32), operands in LDS.
 //   A(i,k) = a[i*ais + k*aks]      B(k,j) = b[k*bks + j*bjs]
 // Fragment map of v_mfma_f32_32x32x2_f32: lane l holds A[i=l&31][k=l>>5], B[k=l>>5][j=l&31].
+// (This file's own: unrolled by 4.  gcm_fused::mma32 unrolls by 8, which gives 48 of the kernels here other code.)
 __device__ __forceinline__ void mma32(f32x16& acc, const float* a, int ais, int aks,
                                       const float* b, int bks, int bjs, int K, int li, int lh) {
   const float* ap = a + li * ais + lh * aks;
@@ -142,29 +143,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_graphconv_fwd(
 size_t fwd_lds_bytes(int waves, int FiP) {
   const int RB = 32 * waves;
   return sizeof(float) * ((size_t)RB * (KT + 1) + KT * FiP + 2 * RB * (FiP + 1) + FiP * 33);
-}
-
-template <int WAVES>
-int launch_fwd(int nct, dim3 grid, size_t lds, hipStream_t s, const float* x, const float* adj,
-               const float* w_rel, const float* b_rel, const float* w_root, float* out, float* agg,
-               int N, int Fi, int Fo, int act) {
-#define GCM_FWD_CASE(NCT)                                                                      \
-  case NCT: {                                                                                  \
-    auto kern = k_graphconv_fwd<WAVES, NCT>;                                                   \
-    gcm_allow_dynamic_lds((const void*)kern, lds); \
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WAVES), lds, s, x, adj, w_rel, b_rel, w_root, out, \
-                       agg, N, Fi, Fo, act);                                                   \
-    break;                                                                                     \
-  }
-  switch (nct) {
-    GCM_FWD_CASE(1)
-    GCM_FWD_CASE(2)
-    GCM_FWD_CASE(3)
-    GCM_FWD_CASE(4)
-    default: return GCM_EUNSUPPORTED;
-  }
-#undef GCM_FWD_CASE
-  return gcm_launch_status();
 }
 
 int pick_waves(int N, int FiP, size_t (*lds_fn)(int, int)) {
@@ -1173,11 +1151,14 @@ extern "C" int gcm_dense_graphconv_fwd(const float* x, const float* adj, const f
   dim3 grid((N + RB - 1) / RB, B);
   const size_t lds = fwd_lds_bytes(waves, FiP);
   hipStream_t s = (hipStream_t)stream;
-  switch (waves) {
-    case 4: return launch_fwd<4>(FiP / 32, grid, lds, s, x, adj, w_rel, b_rel, w_root, out, agg, N, Fi, Fo, act);
-    case 2: return launch_fwd<2>(FiP / 32, grid, lds, s, x, adj, w_rel, b_rel, w_root, out, agg, N, Fi, Fo, act);
-    default: return launch_fwd<1>(FiP / 32, grid, lds, s, x, adj, w_rel, b_rel, w_root, out, agg, N, Fi, Fo, act);
-  }
+  return gcm_pick(
+      [&](auto w, auto nct) {
+        auto kern = k_graphconv_fwd<w(), nct()>;
+        gcm_allow_dynamic_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(64 * w()), lds, s, x, adj, w_rel, b_rel, w_root, out, agg, N, Fi, Fo, act);
+        return gcm_launch_status();
+      },
+      OneOf<4, 2, 1>{waves}, OneOf<1, 2, 3, 4>{FiP / 32});
 }
 
 namespace {
@@ -1198,6 +1179,18 @@ BwdPlan bwd_plan(int B, int N, int Fi, int Fo) {
   p.slab_len = 2 * (size_t)Fo * Fi + Fo;
   p.slabs_bytes = (size_t)B * p.nblk * p.slab_len * sizeof(float);
   return p;
+}
+// kernel 3: the weight gradients out of n_slabs slabs
+void reduce_slabs(const float* slabs, int n_slabs, const BwdPlan& p, float* g_w_rel, float* g_w_root, float* g_b_rel,
+                  int Fi, int Fo, hipStream_t s) {
+  const int slab_len = (int)p.slab_len;
+  hipLaunchKernelGGL(k_reduce_slabs, dim3((slab_len + 15) / 16), dim3(256), 0, s, slabs, n_slabs, slab_len, g_w_rel,
+                     g_w_root, g_b_rel, Fo * Fi, Fo);
+}
+// grid of a persistent kernel over n_tiles row tiles, four to a workgroup: at most per_cu resident workgroups a CU
+int persistent_blocks(int n_tiles, int per_cu) {
+  const int cap = per_cu * gcm_cu_count();
+  return (n_tiles + 3) / 4 < cap ? (n_tiles + 3) / 4 : cap;
 }
 }  // namespace
 
@@ -1228,45 +1221,28 @@ extern "C" int gcm_dense_graphconv_bwd(const float* g_out, const float* out, con
     int rc = gcm_layer_bwd(g_out, out, x, adj, agg, w_rel, w_root, g_x, g_adj, slabs, want_w, B, N,
                            Fi, Fo, act, s);
     if (rc != GCM_OK || !want_w) return rc;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(((int)p.slab_len + 15) / 16), dim3(256), 0, s, slabs, B,
-                       (int)p.slab_len, g_w_rel, g_w_root, g_b_rel, Fo * Fi, Fo);
+    reduce_slabs(slabs, B, p, g_w_rel, g_w_root, g_b_rel, Fi, Fo, s);
     return gcm_launch_status();
   }
   dim3 grid(p.nblk, B);
   const size_t lds1 = bwd_rows_lds_bytes(p.waves, FiP, FoP);
   const size_t lds2 = bwd_adjT_lds_bytes(p.waves, FiP);
-
-#define GCM_BWD_LAUNCH(W, C)                                                                      \
-  {                                                                                               \
-    auto k1 = k_graphconv_bwd_rows<W, C>;                                                         \
-    gcm_allow_dynamic_lds((const void*)k1, lds1); \
-    hipLaunchKernelGGL(k1, grid, dim3(64 * W), lds1, s, g_out, out, x, agg, w_rel, w_root, g_x,   \
-                       g_adj, ws_dagg, slabs, N, Fi, Fo, act, want_w);                            \
-    if (g_x) {                                                                                    \
-      auto k2 = k_graphconv_bwd_adjT<W, C>;                                                       \
-      hipLaunchKernelGGL(k2, grid, dim3(64 * W), lds2, s, adj, ws_dagg, g_x, N, Fi);              \
-    }                                                                                             \
-  }
-#define GCM_BWD_W(W)                                  \
-  switch (nct) {                                      \
-    case 1: GCM_BWD_LAUNCH(W, 1) break;               \
-    case 2: GCM_BWD_LAUNCH(W, 2) break;               \
-    case 3: GCM_BWD_LAUNCH(W, 3) break;               \
-    default: GCM_BWD_LAUNCH(W, 4) break;              \
-  }
-  switch (p.waves) {
-    case 4: GCM_BWD_W(4) break;
-    case 2: GCM_BWD_W(2) break;
-    default: GCM_BWD_W(1) break;
-  }
-#undef GCM_BWD_W
-#undef GCM_BWD_LAUNCH
-  int rc = gcm_launch_status();
+  int rc = gcm_pick(
+      [&](auto w, auto c) {
+        auto k1 = k_graphconv_bwd_rows<w(), c()>;
+        gcm_allow_dynamic_lds((const void*)k1, lds1);
+        hipLaunchKernelGGL(k1, grid, dim3(64 * w()), lds1, s, g_out, out, x, agg, w_rel, w_root, g_x, g_adj, ws_dagg,
+                           slabs, N, Fi, Fo, act, want_w);
+        if (g_x) {
+          auto k2 = k_graphconv_bwd_adjT<w(), c()>;
+          hipLaunchKernelGGL(k2, grid, dim3(64 * w()), lds2, s, adj, ws_dagg, g_x, N, Fi);
+        }
+        return gcm_launch_status();
+      },
+      OneOf<4, 2, 1>{p.waves}, OneOf<1, 2, 3, 4>{nct});
   if (rc != GCM_OK) return rc;
   if (want_w) {
-    const int slab_len = (int)p.slab_len;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((slab_len + 15) / 16), dim3(256), 0, s, slabs,
-                       B * p.nblk, slab_len, g_w_rel, g_w_root, g_b_rel, Fo * Fi, Fo);
+    reduce_slabs(slabs, B * p.nblk, p, g_w_rel, g_w_root, g_b_rel, Fi, Fo, s);
     rc = gcm_launch_status();
   }
   return rc;
@@ -1316,72 +1292,47 @@ static int csr_fwd_impl(const float* x, const int64_t* row_ptr, const int64_t* c
   if (Fi == 32 && (Fo == 32 || Fo == 64) && M >= 32) {   // third generation: exact tiles
     const int n_tiles = (int)((M + 31) / 32);
     const size_t lds3 = sizeof(float) * (4 * 2 * 32 * ((size_t)Fi + 4) + 2 * (size_t)Fo * 2 * (Fi / 2 + 4));
-#define GCM_CSR3(a, b_, hw, hm)                                                                 \
-  if (Fi == a && Fo == b_ && (w != nullptr) == hw && (mask != nullptr) == hm) {                 \
-    auto kern = k_csr_fwd3<a, b_, hw, hm>;                                                            \
-    gcm_allow_dynamic_lds((const void*)kern, lds3);                                             \
-    /* resident workgroups per CU (persistent waves): 3 waves per SIMD by registers, 160 KB of LDS */ \
-    const int by_lds = (int)((160 * 1024) / lds3);                                              \
-    const int per_cu = by_lds < 1 ? 1 : (by_lds > 3 ? 3 : by_lds);                              \
-    const int cap = per_cu * gcm_cu_count();                                                    \
-    const int blocks = (n_tiles + 3) / 4 < cap ? (n_tiles + 3) / 4 : cap;                       \
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds3, s, x, row_ptr, col, w, mask, w_rel, \
-                       b_rel, w_root, out, agg, M, flags, act, n_tiles);                        \
-    return gcm_launch_status();                                                                 \
-  }
-    if (flags && !w && !mask) {   // the checked form (gcm_csr_graphconv_fwd_checked)
-#define GCM_CSR3C(a, b_)                                                                        \
-  if (Fi == a && Fo == b_) {                                                                    \
-    auto kern = k_csr_fwd3<a, b_, false, false, true>;                                          \
-    gcm_allow_dynamic_lds((const void*)kern, lds3);                                             \
-    const int by_lds = (int)((160 * 1024) / lds3);                                              \
-    const int per_cu = by_lds < 1 ? 1 : (by_lds > 3 ? 3 : by_lds);                              \
-    const int cap = per_cu * gcm_cu_count();                                                    \
-    const int blocks = (n_tiles + 3) / 4 < cap ? (n_tiles + 3) / 4 : cap;                       \
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds3, s, x, row_ptr, col, w, mask, w_rel, \
-                       b_rel, w_root, out, agg, M, flags, act, n_tiles);                        \
-    return gcm_launch_status();                                                                 \
-  }
-      GCM_CSR3C(32, 32) GCM_CSR3C(32, 64)
-#undef GCM_CSR3C
+    // resident workgroups per CU (persistent waves): 3 waves per SIMD by registers, 160 KB of LDS
+    const int by_lds = (int)((160 * 1024) / lds3);
+    const int blocks = persistent_blocks(n_tiles, by_lds < 1 ? 1 : (by_lds > 3 ? 3 : by_lds));
+    auto launch3 = [&](auto fo, auto hw, auto hm, auto chk) {
+      auto kern = k_csr_fwd3<32, fo(), bool(hw()), bool(hm()), bool(chk())>;
+      gcm_allow_dynamic_lds((const void*)kern, lds3);
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds3, s, x, row_ptr, col, w, mask, w_rel, b_rel, w_root, out,
+                         agg, M, flags, act, n_tiles);
+      return gcm_launch_status();
+    };
+    if (flags) {   // the checked form (gcm_csr_graphconv_fwd_checked); edge weights / k-hop mask: none
+      if (w || mask) return GCM_EUNSUPPORTED;
+      return gcm_pick([&](auto fo) { return launch3(fo, gcm_c<0>, gcm_c<0>, gcm_c<1>); }, OneOf<32, 64>{Fo});
     }
-    if (flags) return GCM_EUNSUPPORTED;   // (edge weights / k-hop mask: no checked form)
-    GCM_CSR3(32, 32, false, false) GCM_CSR3(32, 32, true, false) GCM_CSR3(32, 32, false, true)
-    GCM_CSR3(32, 32, true, true) GCM_CSR3(32, 64, false, false) GCM_CSR3(32, 64, true, false)
-    GCM_CSR3(32, 64, false, true) GCM_CSR3(32, 64, true, true)
-#undef GCM_CSR3
+    return gcm_pick([&](auto fo, auto hw, auto hm) { return launch3(fo, hw, hm, gcm_c<0>); }, OneOf<32, 64>{Fo},
+                    Flag{w != nullptr}, Flag{mask != nullptr});
   }
   if (Fi <= 64 && Fo <= 64) {   // second-generation kernel
-    const int NCT = FiP / 32, NHT = round32(Fo) / 32;
+    const int NHT = round32(Fo) / 32;
     const size_t lds2 = sizeof(float) * ((size_t)128 * (FiP + 1) + 2 * FiP * (32 * NHT + 1) + 1) + 8 +
                         sizeof(int) * (128 + 2 + 1024) + sizeof(float) * 1024;
-#define GCM_CSR2(a, b_)                                                                         \
-  if (NCT == a && NHT == b_) {                                                                  \
-    auto kern = k_csr_fwd2<a, b_>;                                                              \
-    gcm_allow_dynamic_lds((const void*)kern, lds2);                                                                                           \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds2, s, x, row_ptr, col, w, mask, w_rel, b_rel,  \
-                       w_root, out, agg, M, Fi, Fo, act);                                       \
-    return gcm_launch_status();                                                                 \
-  }
-    GCM_CSR2(1, 1) GCM_CSR2(1, 2) GCM_CSR2(2, 1) GCM_CSR2(2, 2)
-#undef GCM_CSR2
+    return gcm_pick(
+        [&](auto nct, auto nht) {
+          auto kern = k_csr_fwd2<nct(), nht()>;
+          gcm_allow_dynamic_lds((const void*)kern, lds2);
+          hipLaunchKernelGGL(kern, grid, dim3(256), lds2, s, x, row_ptr, col, w, mask, w_rel, b_rel, w_root, out, agg,
+                             M, Fi, Fo, act);
+          return gcm_launch_status();
+        },
+        OneOf<1, 2>{FiP / 32}, OneOf<1, 2>{NHT});
   }
   const size_t lds = csr_fwd_lds_bytes(FiP);
-#define GCM_CSR_FWD(NCT)                                                                        \
-  {                                                                                             \
-    auto kern = k_csr_graphconv_fwd<NCT>;                                                       \
-    gcm_allow_dynamic_lds((const void*)kern, lds); \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, x, row_ptr, col, w, mask, w_rel, b_rel,   \
-                       w_root, out, agg, M, Fi, Fo, act);                                       \
-  }
-  switch (FiP / 32) {
-    case 1: GCM_CSR_FWD(1) break;
-    case 2: GCM_CSR_FWD(2) break;
-    case 3: GCM_CSR_FWD(3) break;
-    default: GCM_CSR_FWD(4) break;
-  }
-#undef GCM_CSR_FWD
-  return gcm_launch_status();
+  return gcm_pick(
+      [&](auto nct) {
+        auto kern = k_csr_graphconv_fwd<nct()>;
+        gcm_allow_dynamic_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, x, row_ptr, col, w, mask, w_rel, b_rel, w_root, out, agg, M,
+                           Fi, Fo, act);
+        return gcm_launch_status();
+      },
+      OneOf<1, 2, 3, 4>{FiP / 32});
 }
 
 extern "C" size_t gcm_csr_graphconv_bwd_workspace_bytes(int64_t M, int Fi, int Fo) {
@@ -1417,72 +1368,49 @@ extern "C" int gcm_csr_graphconv_bwd(const float* g_out, const float* out, const
   const size_t lds1 = bwd_rows_lds_bytes(p.waves, FiP, FoP);
   const int N = (int)M;
   float* no_adj = nullptr;
-  bool rows_done = false;
   if (Fi == 32 && Fo == 32 && !mask && !g_w && M >= 32 && (!g_x || E == 0 || (col_ptr && rows && perm))) {
     // third generation: row-local adjoint and transpose aggregation in one pass
     const int n_tiles = (int)((M + 31) / 32);
     const size_t lds3 = sizeof(float) * (4 * 3 * 32 * 36 + 2 * 2 * 32 * 20);
-    const int cap = 2 * gcm_cu_count();   // two resident workgroups per CU (LDS)
-    const int blocks = (n_tiles + 3) / 4 < cap ? (n_tiles + 3) / 4 : cap;
+    const int blocks = persistent_blocks(n_tiles, 2);   // two resident workgroups per CU (LDS)
     const bool need_x = g_x != nullptr, gather = need_x && E > 0;
     // (no edges: the CSC view may be absent - the gather loop never runs, col_ptr is not read)
-#define GCM_BWD3(hw, nx)                                                                        \
-  if ((w != nullptr) == hw && need_x == nx) {                                                   \
-    auto kern = k_csr_bwd3<hw, nx>;                                                             \
-    gcm_allow_dynamic_lds((const void*)kern, lds3);                                             \
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds3, s, g_out, out, x, agg,              \
-                       gather ? col_ptr : nullptr, rows, perm, w, w_rel, w_root, g_x, slabs, M, act, \
-                       n_tiles);                                                                \
-  }
-    GCM_BWD3(false, false) GCM_BWD3(true, false) GCM_BWD3(false, true) GCM_BWD3(true, true)
-#undef GCM_BWD3
-    int rc3 = gcm_launch_status();
+    int rc3 = gcm_pick(
+        [&](auto hw, auto nx) {
+          auto kern = k_csr_bwd3<bool(hw()), bool(nx())>;
+          gcm_allow_dynamic_lds((const void*)kern, lds3);
+          hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds3, s, g_out, out, x, agg, gather ? col_ptr : nullptr,
+                             rows, perm, w, w_rel, w_root, g_x, slabs, M, act, n_tiles);
+          return gcm_launch_status();
+        },
+        Flag{w != nullptr}, Flag{need_x});
     if (rc3 != GCM_OK) return rc3;
-    if (want_w) {
-      const int slab_len = (int)p.slab_len;
-      hipLaunchKernelGGL(k_reduce_slabs, dim3((slab_len + 15) / 16), dim3(256), 0, s, slabs, blocks,
-                         slab_len, g_w_rel, g_w_root, g_b_rel, Fo * Fi, Fo);
-    }
+    if (want_w) reduce_slabs(slabs, blocks, p, g_w_rel, g_w_root, g_b_rel, Fi, Fo, s);
     return gcm_launch_status();
   }
+  int rc;
   if (Fi <= 64 && Fo <= 64 && p.waves == 4) {   // second-generation row-local kernel
-    const int NCT = FiP / 32, NHT = FoP / 32;
     const size_t lds2 = sizeof(float) * ((size_t)128 * (FoP + 1) + 2 * FoP * (FiP + 1) + 4 * 1024 + 256);
-#define GCM_ROWS2(a, b_)                                                                        \
-  if (NCT == a && NHT == b_) {                                                                  \
-    auto kern = k_rows_bwd2<a, b_>;                                                             \
-    gcm_allow_dynamic_lds((const void*)kern, lds2);                                                                                           \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds2, s, g_out, out, x, agg, w_rel, w_root, g_x,  \
-                       ws_dagg, slabs, M, Fi, Fo, act, want_w);                                 \
-    rows_done = true;                                                                           \
+    rc = gcm_pick(
+        [&](auto nct_, auto nht) {
+          auto kern = k_rows_bwd2<nct_(), nht()>;
+          gcm_allow_dynamic_lds((const void*)kern, lds2);
+          hipLaunchKernelGGL(kern, grid, dim3(256), lds2, s, g_out, out, x, agg, w_rel, w_root, g_x, ws_dagg, slabs, M,
+                             Fi, Fo, act, want_w);
+          return gcm_launch_status();
+        },
+        OneOf<1, 2>{nct}, OneOf<1, 2>{FoP / 32});
+  } else {
+    rc = gcm_pick(
+        [&](auto w_, auto c) {
+          auto k1 = k_graphconv_bwd_rows<w_(), c()>;
+          gcm_allow_dynamic_lds((const void*)k1, lds1);
+          hipLaunchKernelGGL(k1, grid, dim3(64 * w_()), lds1, s, g_out, out, x, agg, w_rel, w_root, g_x, no_adj, ws_dagg,
+                             slabs, N, Fi, Fo, act, want_w);
+          return gcm_launch_status();
+        },
+        OneOf<4, 2, 1>{p.waves}, OneOf<1, 2, 3, 4>{nct});
   }
-    GCM_ROWS2(1, 1) GCM_ROWS2(1, 2) GCM_ROWS2(2, 1) GCM_ROWS2(2, 2)
-#undef GCM_ROWS2
-  }
-  if (!rows_done) {
-#define GCM_CSR_BWD(W, C)                                                                       \
-  {                                                                                             \
-    auto k1 = k_graphconv_bwd_rows<W, C>;                                                       \
-    gcm_allow_dynamic_lds((const void*)k1, lds1); \
-    hipLaunchKernelGGL(k1, grid, dim3(64 * W), lds1, s, g_out, out, x, agg, w_rel, w_root, g_x, \
-                       no_adj, ws_dagg, slabs, N, Fi, Fo, act, want_w);                         \
-  }
-#define GCM_CSR_BWD_W(W)                           \
-  switch (nct) {                                   \
-    case 1: GCM_CSR_BWD(W, 1) break;               \
-    case 2: GCM_CSR_BWD(W, 2) break;               \
-    case 3: GCM_CSR_BWD(W, 3) break;               \
-    default: GCM_CSR_BWD(W, 4) break;              \
-  }
-  switch (p.waves) {
-    case 4: GCM_CSR_BWD_W(4) break;
-    case 2: GCM_CSR_BWD_W(2) break;
-    default: GCM_CSR_BWD_W(1) break;
-  }
-#undef GCM_CSR_BWD_W
-#undef GCM_CSR_BWD
-  }
-  int rc = gcm_launch_status();
   if (rc != GCM_OK) return rc;
   if (g_x && E > 0) {
     const int64_t total = M * Fi;
@@ -1493,10 +1421,6 @@ extern "C" int gcm_csr_graphconv_bwd(const float* g_out, const float* out, const
     hipLaunchKernelGGL(k_csr_edge_grad, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, x,
                        ws_dagg, col_ptr, rows, perm, mask, g_w, M, Fi);
   }
-  if (want_w) {
-    const int slab_len = (int)p.slab_len;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((slab_len + 15) / 16), dim3(256), 0, s, slabs, p.nblk,
-                       slab_len, g_w_rel, g_w_root, g_b_rel, Fo * Fi, Fo);
-  }
+  if (want_w) reduce_slabs(slabs, p.nblk, p, g_w_rel, g_w_root, g_b_rel, Fi, Fo, s);
   return gcm_launch_status();
 }

@@ -127,25 +127,27 @@ __global__ __launch_bounds__(256) void k_sparsemax_bwd(const float* __restrict__
 
 constexpr int MAXC = 16;   // N <= 1024, as gcm_learned_select_*
 
-}  // namespace
+// launch(grid, block, c): a kernel's <c> instantiation, c = the columns of 64 candidates a lane holds
+template <typename Launch>
+int sparsemax_launch(int B, int N, Launch launch) {
+  const int cols = (N + 63) / 64;
+  return gcm_pick(
+      [&](auto c) {
+        launch(dim3((B + 3) / 4), dim3(256), c);
+        return gcm_launch_status();
+      },
+      OneOf<1, 2, 4, 8, MAXC>{cols <= 1 ? 1 : cols <= 2 ? 2 : cols <= 4 ? 4 : cols <= 8 ? 8 : MAXC});
+}
 
-#define GCM_SPARSEMAX_LAUNCH(K, ...)                                                              \
-  do {                                                                                            \
-    const dim3 grid((B + 3) / 4), block(256);                                                     \
-    const int cols = (N + 63) / 64;                                                               \
-    if (cols <= 1) hipLaunchKernelGGL(K<1>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__);    \
-    else if (cols <= 2) hipLaunchKernelGGL(K<2>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (cols <= 4) hipLaunchKernelGGL(K<4>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (cols <= 8) hipLaunchKernelGGL(K<8>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(K<MAXC>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__);           \
-  } while (0)
+}  // namespace
 
 extern "C" int gcm_learned_sparsemax_fwd(const float* logits, const int64_t* cur_idx, float* adj,
                                          float* soft, int B, int N, gcm_stream_t stream) {
   GCM_REQUIRE(logits && cur_idx && adj && soft && B > 0 && N > 0);
   if (N > 64 * MAXC) return GCM_EUNSUPPORTED;
-  GCM_SPARSEMAX_LAUNCH(k_sparsemax_fwd, logits, cur_idx, adj, soft, B, N);
-  return gcm_launch_status();
+  return sparsemax_launch(B, N, [&](dim3 grid, dim3 block, auto c) {
+    hipLaunchKernelGGL(k_sparsemax_fwd<c()>, grid, block, 0, (hipStream_t)stream, logits, cur_idx, adj, soft, B, N);
+  });
 }
 
 extern "C" int gcm_learned_sparsemax_bwd(const float* g_adj, const float* soft,
@@ -153,6 +155,7 @@ extern "C" int gcm_learned_sparsemax_bwd(const float* g_adj, const float* soft,
                                          gcm_stream_t stream) {
   GCM_REQUIRE(g_adj && soft && cur_idx && g_logits && B > 0 && N > 0);
   if (N > 64 * MAXC) return GCM_EUNSUPPORTED;
-  GCM_SPARSEMAX_LAUNCH(k_sparsemax_bwd, g_adj, soft, cur_idx, g_logits, B, N);
-  return gcm_launch_status();
+  return sparsemax_launch(B, N, [&](dim3 grid, dim3 block, auto c) {
+    hipLaunchKernelGGL(k_sparsemax_bwd<c()>, grid, block, 0, (hipStream_t)stream, g_adj, soft, cur_idx, g_logits, B, N);
+  });
 }

@@ -378,11 +378,6 @@ __global__ __launch_bounds__(256) void k_gnodes_scan(
 
 }  // namespace gcm_fused
 
-// instantiated EXACT shapes of the persistent forward
-#define GCM_RSHAPES_N(X, a) \
-  X(a, 1, 1, 1) X(a, 1, 1, 2) X(a, 1, 2, 1) X(a, 1, 2, 2) X(a, 2, 1, 1) X(a, 2, 1, 2) X(a, 2, 2, 1) X(a, 2, 2, 2)
-#define GCM_RSHAPES(X) GCM_RSHAPES_N(X, 1) GCM_RSHAPES_N(X, 2) GCM_RSHAPES_N(X, 3) GCM_RSHAPES_N(X, 4)
-
 extern "C" int gcm_dense_rollout_persistent_fwd(const float* obs, float* nodes_all, float* adj_all,
                                int64_t* count_all, int64_t* cur_all,
                                const gcm_selector_desc* selectors, int n_selectors,
@@ -413,15 +408,11 @@ extern "C" int gcm_dense_rollout_persistent_fwd(const float* obs, float* nodes_a
     }
   }
   gcm_fused::Gnn2 P{w_rel1, b_rel1, w_root1, w_rel2, b_rel2, w_root2, act1, act2};
-  const int NT = N / 32, NCT = F / 32, NHT = H1 / 32, N2T = H2 / 32;
-#define GCM_R(a, b_, c, d)                                                                     \
-  if (NT == a && NCT == b_ && NHT == c && N2T == d)                                            \
-    return gcm_fused::launch_rollout<a, b_, c, d>(s, obs, nodes_all, adj_all, count_all,       \
-                                                  cur_all, E, P, mx_all, h1_all, agg1_all,     \
-                                                  agg2_all, flags, T, B, history);
-  GCM_RSHAPES(GCM_R)
-#undef GCM_R
-  return GCM_EUNSUPPORTED;
+  return gcm_fused::pick_shape(N, F, H1, H2, [&](auto nt, auto nct, auto nht, auto n2t) {   // exact shapes only
+    return gcm_fused::launch_rollout<nt(), nct(), nht(), n2t()>(s, obs, nodes_all, adj_all, count_all, cur_all, E, P,
+                                                                mx_all, h1_all, agg1_all, agg2_all, flags, T, B,
+                                                                history);
+  });
 }
 
 extern "C" int gcm_dense_gnodes_scan(const float* Q_all, const float* pobs_all,
@@ -436,16 +427,13 @@ extern "C" int gcm_dense_gnodes_scan(const float* Q_all, const float* pobs_all,
   const size_t lds = sizeof(float) * 2 * (size_t)N * F + sizeof(int) * (size_t)T;
   if (lds > 160 * 1024) return GCM_EUNSUPPORTED;   // T > ~24k steps: the caller's step-by-step schedule
   const int nper = (N * F + 255) / 256;
-#define GCM_SCAN(P)                                                                              \
-  {                                                                                              \
-    gcm_allow_dynamic_lds((const void*)gcm_fused::k_gnodes_scan<P>, lds); \
-    hipLaunchKernelGGL(gcm_fused::k_gnodes_scan<P>, dim3(B), dim3(256), lds, s, Q_all, pobs_all, \
-                       g_nodes_T, cur_all, count_all, g_obs_all, g_nodes_0, T, B, N, F);         \
-    return gcm_launch_status();                                                                  \
-  }
-  if (nper <= 4) GCM_SCAN(4)
-  if (nper <= 8) GCM_SCAN(8)
-  if (nper <= 16) GCM_SCAN(16)
-  GCM_SCAN(32)
-#undef GCM_SCAN
+  return gcm_pick(
+      [&](auto per) {
+        auto kern = gcm_fused::k_gnodes_scan<per()>;
+        gcm_allow_dynamic_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, s, Q_all, pobs_all, g_nodes_T, cur_all, count_all, g_obs_all,
+                           g_nodes_0, T, B, N, F);
+        return gcm_launch_status();
+      },
+      OneOf<4, 8, 16, 32>{nper <= 4 ? 4 : nper <= 8 ? 8 : nper <= 16 ? 16 : 32});
 }

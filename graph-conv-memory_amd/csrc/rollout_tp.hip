@@ -251,27 +251,26 @@ extern "C" int gcm_dense_rollout_tp_fwd(const float* obs, const gcm_selector_des
   const int cap = 2 * gcm_cu_count();
   const int grid = (n_tiles + 3) / 4 < cap ? (n_tiles + 3) / 4 : cap;
   hipStream_t s = (hipStream_t)stream;
-#define GCM_TP1(a, b_)                                                                                            \
-  if (F == a && H1 == b_) {                                                                                       \
-    auto k1 = gcm_rtp::k_rollout_tp_l1<a, b_>;                                                                    \
-    const size_t lds1 = sizeof(float) * ((size_t)2 * a * (b_ + 1) + (size_t)4 * 32 * (2 * a + 1));               \
-    gcm_allow_dynamic_lds((const void*)k1, lds1);                                                                 \
-    hipLaunchKernelGGL(k1, dim3(grid), dim3(256), lds1, s, obs, hp, params, act1, cache_h1, cache_agg1,           \
-                       cache_nodes, nodes, adj, count, B, T, N, Tc, n_tiles);                                     \
-  }
-  GCM_TP1(32, 32) GCM_TP1(64, 32) GCM_TP1(32, 64) GCM_TP1(64, 64)
-#undef GCM_TP1
-  int rc = gcm_launch_status();
+  const OneOf<32, 64> h1_{H1};
+  const int rc = gcm_pick(
+      [&](auto a, auto b) {
+        auto k1 = gcm_rtp::k_rollout_tp_l1<a(), b()>;
+        const size_t lds1 = sizeof(float) * ((size_t)2 * a() * (b() + 1) + (size_t)4 * 32 * (2 * a() + 1));
+        gcm_allow_dynamic_lds((const void*)k1, lds1);
+        hipLaunchKernelGGL(k1, dim3(grid), dim3(256), lds1, s, obs, hp, params, act1, cache_h1, cache_agg1, cache_nodes,
+                           nodes, adj, count, B, T, N, Tc, n_tiles);
+        return gcm_launch_status();
+      },
+      OneOf<32, 64>{F}, h1_);
   if (rc) return rc;
-#define GCM_TP2(b_)                                                                                               \
-  if (H1 == b_) {                                                                                                 \
-    auto k2 = gcm_rtp::k_rollout_tp_l2<b_>;                                                                       \
-    const size_t lds2 = sizeof(float) * ((size_t)2 * b_ * 65 + (size_t)4 * 32 * (2 * b_ + 1));                   \
-    gcm_allow_dynamic_lds((const void*)k2, lds2);                                                                 \
-    hipLaunchKernelGGL(k2, dim3(grid), dim3(256), lds2, s, hp, params, F, act2, cache_h1, mx_all, records,        \
-                       rec_stride, lay, record, flags, B, T, N, Tc, H2, n_tiles);                                 \
-  }
-  GCM_TP2(32) GCM_TP2(64)
-#undef GCM_TP2
-  return gcm_launch_status();
+  return gcm_pick(
+      [&](auto b) {
+        auto k2 = gcm_rtp::k_rollout_tp_l2<b()>;
+        const size_t lds2 = sizeof(float) * ((size_t)2 * b() * 65 + (size_t)4 * 32 * (2 * b() + 1));
+        gcm_allow_dynamic_lds((const void*)k2, lds2);
+        hipLaunchKernelGGL(k2, dim3(grid), dim3(256), lds2, s, hp, params, F, act2, cache_h1, mx_all, records,
+                           rec_stride, lay, record, flags, B, T, N, Tc, H2, n_tiles);
+        return gcm_launch_status();
+      },
+      h1_);
 }

@@ -1456,17 +1456,16 @@ static int rows_bptt_impl(const float* const* saved_host, const float* const* gm
       if (rc) return rc;
       continue;
     }
-#define GCM_RB(a, b_, cc)                                                                          \
-  if (fp == a && hp == b_ && h2p == cc)                                                            \
-    rc = cache_h1 ? gcm_rows::launch_bptt<a, b_, cc, 3>(s, per, tab, gcm_rows::Hist{}, ns, gmx_stride_b,   \
-                                                        gmx_stride_h, w_rel2, w_root2, act1, act2, lay, sl, B, \
-                                                        N, F, H1, H2, 0, caches)                               \
-                  : gcm_rows::launch_bptt<a, b_, cc, 0>(s, per, tab, gcm_rows::Hist{}, ns, gmx_stride_b,   \
-                                                        gmx_stride_h, w_rel2, w_root2, act1, act2, lay, sl, B, \
-                                                        N, F, H1, H2, deg_term);
-    GCM_RB(32, 32, 32) GCM_RB(32, 32, 64) GCM_RB(32, 64, 32) GCM_RB(32, 64, 64)
-    GCM_RB(64, 32, 32) GCM_RB(64, 32, 64) GCM_RB(64, 64, 32) GCM_RB(64, 64, 64)
-#undef GCM_RB
+    rc = gcm_pick(
+        [&](auto a, auto b, auto cc) {
+          return cache_h1 ? gcm_rows::launch_bptt<a(), b(), cc(), 3>(s, per, tab, gcm_rows::Hist{}, ns, gmx_stride_b,
+                                                                     gmx_stride_h, w_rel2, w_root2, act1, act2, lay, sl,
+                                                                     B, N, F, H1, H2, 0, caches)
+                          : gcm_rows::launch_bptt<a(), b(), cc(), 0>(s, per, tab, gcm_rows::Hist{}, ns, gmx_stride_b,
+                                                                     gmx_stride_h, w_rel2, w_root2, act1, act2, lay, sl,
+                                                                     B, N, F, H1, H2, deg_term);
+        },
+        OneOf<32, 64>{fp}, OneOf<32, 64>{hp}, OneOf<32, 64>{h2p});
     if (rc) return rc;
   }
   return gcm_sum_slabs_acc(slabs, total_slabs, (int)P, g_params_prev, g_params, stream);
@@ -1507,16 +1506,13 @@ extern "C" int gcm_dense_rollout_bwd_params(const float* g_mx_all, long gmx_stri
   hipStream_t s = (hipStream_t)stream;
   const int fp = F <= 32 ? 32 : 64, hp = H1 <= 32 ? 32 : 64, h2p = H2 <= 32 ? 32 : 64;
   float* slabs = (float*)workspace;
-  int rc = GCM_EUNSUPPORTED;
   const gcm_rows::StepTable none{};
-#define GCM_RH(a, b_, cc)                                                                          \
-  if (fp == a && hp == b_ && h2p == cc)                                                            \
-    rc = gcm_rows::launch_bptt<a, b_, cc, 1>(s, grid, none, hs, T, gmx_stride_b, gmx_stride_h,  \
-                                                w_rel2, w_root2, act1, act2, lay, slabs, B, N, F,  \
-                                                H1, H2);
-  GCM_RH(32, 32, 32) GCM_RH(32, 32, 64) GCM_RH(32, 64, 32) GCM_RH(32, 64, 64)
-  GCM_RH(64, 32, 32) GCM_RH(64, 32, 64) GCM_RH(64, 64, 32) GCM_RH(64, 64, 64)
-#undef GCM_RH
+  const int rc = gcm_pick(
+      [&](auto a, auto b, auto cc) {
+        return gcm_rows::launch_bptt<a(), b(), cc(), 1>(s, grid, none, hs, T, gmx_stride_b, gmx_stride_h, w_rel2,
+                                                        w_root2, act1, act2, lay, slabs, B, N, F, H1, H2);
+      },
+      OneOf<32, 64>{fp}, OneOf<32, 64>{hp}, OneOf<32, 64>{h2p});
   if (rc) return rc;
   (void)P;
   return gcm_sum_slabs(slabs, grid, (int)P, g_params, stream);

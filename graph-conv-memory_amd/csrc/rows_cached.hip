@@ -1124,66 +1124,46 @@ extern "C" int gcm_dense_rows_step_cached_ws(const float* obs, float* nodes, flo
                                                      cur_host, (hipStream_t)stream);
     if (rc != GCM_EUNSUPPORTED) return rc;
   }
+  const OneOf<32, 64> f_{F}, h1_{H1};
   if (weight_image) {
-#define GCM_RI(a, b_)                                                                                            \
-  if (F == a && H1 == b_) {                                                                                      \
-    if (sel_row)                                                                                                 \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_sel<a, b_>), dim3(B), dim3(64), 0, (hipStream_t)stream,       \
-                         obs, nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1,          \
-                         cache_nodes, saved, lay, flags, B, N, H2, cur_host, sel_row);                               \
-    else if ((has_bias & GCM_STEP_IMG_V4) && a == 32 && b_ == 32 && H2 <= 32 && cur_host >= 0 &&                  \
-             !(has_bias & GCM_STEP_ONE_WAVE))                                                                     \
-      hipLaunchKernelGGL(gcm_rows::k_step_rows_cached_img4b, dim3(B), dim3(128), 0, (hipStream_t)stream, obs, nodes,  \
-                         adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1, cache_nodes, saved,  \
-                         lay, flags, B, N, H2, cur_host);                                                             \
-    else if ((has_bias & GCM_STEP_IMG_V4) && a == 32 && b_ == 32 && H2 <= 32)                                     \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_img4<a, b_, true>), dim3(B), dim3(64), 0,                     \
-                         (hipStream_t)stream, obs, nodes, adj, count, HM, params, weight_image, act1, act2,           \
-                         cache_h1, cache_agg1, cache_nodes, saved, lay, flags, B, N, H2, cur_host);                   \
-    else if (has_bias & GCM_STEP_IMG_V4)                                                                          \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_img4<a, b_>), dim3(B), dim3(64), 0, (hipStream_t)stream,      \
-                         obs, nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1,          \
-                         cache_nodes, saved, lay, flags, B, N, H2, cur_host);                                        \
-    else                                                                                                         \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_img<a, b_>), dim3(B), dim3(64), 0, (hipStream_t)stream,       \
-                         obs, nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1,          \
-                         cache_nodes, saved, lay, flags, B, N, H2, cur_host);                                        \
-    return gcm_launch_status();                                                                                  \
-  }
-    GCM_RI(32, 32) GCM_RI(64, 32) GCM_RI(32, 64) GCM_RI(64, 64)
-#undef GCM_RI
+    // one wave (or `threads`) per graph; extra: what a kernel takes behind the common arguments
+    auto go = [&](auto kern, int threads, auto... extra) {
+      hipLaunchKernelGGL(kern, dim3(B), dim3(threads), 0, (hipStream_t)stream, obs, nodes, adj, count, HM, params,
+                         weight_image, act1, act2, cache_h1, cache_agg1, cache_nodes, saved, lay, flags, B, N, H2,
+                         cur_host, extra...);
+      return gcm_launch_status();
+    };
+    const bool v4 = (has_bias & GCM_STEP_IMG_V4) != 0;
+    const int rc = gcm_pick(
+        [&](auto a, auto b) {
+          const bool small = a() == 32 && b() == 32 && H2 <= 32;
+          if (sel_row) return go(gcm_rows::k_step_rows_cached_sel<a(), b()>, 64, sel_row);
+          if (v4 && small && cur_host >= 0 && !(has_bias & GCM_STEP_ONE_WAVE))
+            return go(gcm_rows::k_step_rows_cached_img4b, 128);
+          if (v4 && small) return go(gcm_rows::k_step_rows_cached_img4<a(), b(), true>, 64);
+          if (v4) return go(gcm_rows::k_step_rows_cached_img4<a(), b()>, 64);
+          return go(gcm_rows::k_step_rows_cached_img<a(), b()>, 64);
+        },
+        f_, h1_);
+    if (rc != GCM_EUNSUPPORTED) return rc;
     // other widths: the padded form
-    const int fp = F <= 32 ? 32 : 64, hp = H1 <= 32 ? 32 : 64;
-#define GCM_RG(a, b_)                                                                                            \
-  if (fp == a && hp == b_) {                                                                                     \
-    if (sel_row)                                                                                                 \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_gen<a, b_, true>), dim3(B), dim3(64), 0, (hipStream_t)stream, \
-                         obs, nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1,          \
-                         cache_nodes, saved, lay, flags, B, N, H2, cur_host, sel_row, F, H1);                        \
-    else                                                                                                         \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_gen<a, b_, false>), dim3(B), dim3(64), 0,                    \
-                         (hipStream_t)stream, obs, nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, \
-                         cache_agg1, cache_nodes, saved, lay, flags, B, N, H2, cur_host, (const float*)nullptr, F,   \
-                         H1);                                                                                        \
-    return gcm_launch_status();                                                                                  \
-  }
-    GCM_RG(32, 32) GCM_RG(64, 32) GCM_RG(32, 64) GCM_RG(64, 64)
-#undef GCM_RG
-    return GCM_EUNSUPPORTED;
+    return gcm_pick(
+        [&](auto a, auto b) {
+          if (sel_row) return go(gcm_rows::k_step_rows_cached_gen<a(), b(), true>, 64, sel_row, F, H1);
+          return go(gcm_rows::k_step_rows_cached_gen<a(), b(), false>, 64, (const float*)nullptr, F, H1);
+        },
+        OneOf<32, 64>{F <= 32 ? 32 : 64}, OneOf<32, 64>{H1 <= 32 ? 32 : 64});
   }
   const size_t lds = sizeof(float) * (2 * (size_t)H1 * (F + 1) + 2 * (size_t)64 * (H1 + 1) + 4 * 128);
-#define GCM_RC(a, b_)                                                                                           \
-  if (F == a && H1 == b_) {                                                                                     \
-    auto kern = gcm_rows::k_step_rows_cached<a, b_>;                                                            \
-    gcm_allow_dynamic_lds((const void*)kern, lds);                                                              \
-    hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), lds, (hipStream_t)stream, obs, nodes, adj, count, E, \
-                       params, act1, act2, cache_h1, cache_agg1, cache_nodes, saved, lay, flags, B, N, H2,      \
-                       cur_host);                                                                              \
-    return gcm_launch_status();                                                                                 \
-  }
-  GCM_RC(32, 32) GCM_RC(64, 32) GCM_RC(32, 64) GCM_RC(64, 64)
-#undef GCM_RC
-  return GCM_EUNSUPPORTED;
+  return gcm_pick(
+      [&](auto a, auto b) {
+        auto kern = gcm_rows::k_step_rows_cached<a(), b()>;
+        gcm_allow_dynamic_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), lds, (hipStream_t)stream, obs, nodes, adj, count, E,
+                           params, act1, act2, cache_h1, cache_agg1, cache_nodes, saved, lay, flags, B, N, H2, cur_host);
+        return gcm_launch_status();
+      },
+      f_, h1_);
 }
 
 // hops of forward temporal selectors as the steady-state step wants them: distinct, descending, 0 < h < N; -> count,
@@ -1233,21 +1213,17 @@ extern "C" int gcm_dense_rows_step_cached_roll(const float* obs, float* nodes, c
   }
   E.n_hops = n;
   const gcm_rows::SavedLayout lay = gcm_rows::make_layout(B, N, F, H1, H2);
-#define GCM_RR(a, b_)                                                                                             \
-  if (F == a && H1 == b_) {                                                                                       \
-    if (a == 32 && b_ == 32 && H2 <= 32)                                                                          \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_roll<a, b_, true>), dim3(B), dim3(192), 0,                     \
-                         (hipStream_t)stream, obs, nodes, E, self, params, weight_image, act1, act2, cache_h1,        \
-                         cache_agg1, cache_nodes, saved, lay, record, flags, B, N, H2, t_abs % N);                    \
-    else                                                                                                          \
-      hipLaunchKernelGGL((gcm_rows::k_step_rows_cached_roll<a, b_>), dim3(B), dim3(192), 0, (hipStream_t)stream,      \
-                         obs, nodes, E, self, params, weight_image, act1, act2, cache_h1, cache_agg1, cache_nodes,    \
-                         saved, lay, record, flags, B, N, H2, t_abs % N);                                             \
-    return gcm_launch_status();                                                                                   \
-  }
-  GCM_RR(32, 32) GCM_RR(64, 32) GCM_RR(32, 64) GCM_RR(64, 64)
-#undef GCM_RR
-  return GCM_EUNSUPPORTED;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(B), dim3(192), 0, (hipStream_t)stream, obs, nodes, E, self, params, weight_image,
+                       act1, act2, cache_h1, cache_agg1, cache_nodes, saved, lay, record, flags, B, N, H2, t_abs % N);
+    return gcm_launch_status();
+  };
+  return gcm_pick(
+      [&](auto a, auto b) {
+        if (a() == 32 && b() == 32 && H2 <= 32) return go(gcm_rows::k_step_rows_cached_roll<a(), b(), true>);
+        return go(gcm_rows::k_step_rows_cached_roll<a(), b()>);
+      },
+      OneOf<32, 64>{F}, OneOf<32, 64>{H1});
 }
 
 #ifdef GCM_DEBUG_ABI   // libgcm_hip_debug.so only (include/gcm_hip_debug.h)
@@ -1274,14 +1250,15 @@ extern "C" int gcm_debug_time_cached_rollout(const float* obs_all, float* nodes,
   const gcm_rows::CachedLayout lay = gcm_rows::make_cached_layout(B, N, H1, H2);
   const gcm_rows::HopMask HM = gcm_rows::make_hop_mask(E);
   for (int t = 0; t < T; ++t) {
-#define GCM_RT(a, b_)                                                                                           \
-  if (F == a && H1 == b_)                                                                                       \
-    hipExtLaunchKernelGGL((gcm_rows::k_step_rows_cached_img<a, b_>), dim3(B), dim3(64), 0, (hipStream_t)stream,  \
-                          (hipEvent_t)start_events[t], (hipEvent_t)stop_events[t], 0,                            \
-                          obs_all + (size_t)t * B * F, nodes, adj, count, HM, params, weight_image, act1, act2,  \
-                          cache_h1, cache_agg1, cache_nodes, saved_per_step[t], lay, flags, B, N, H2, t);
-    GCM_RT(32, 32) GCM_RT(64, 32) GCM_RT(32, 64) GCM_RT(64, 64)
-#undef GCM_RT
+    gcm_pick(
+        [&](auto a, auto b) {
+          hipExtLaunchKernelGGL((gcm_rows::k_step_rows_cached_img<a(), b()>), dim3(B), dim3(64), 0, (hipStream_t)stream,
+                                (hipEvent_t)start_events[t], (hipEvent_t)stop_events[t], 0, obs_all + (size_t)t * B * F,
+                                nodes, adj, count, HM, params, weight_image, act1, act2, cache_h1, cache_agg1,
+                                cache_nodes, saved_per_step[t], lay, flags, B, N, H2, t);
+          return GCM_OK;
+        },
+        OneOf<32, 64>{F}, OneOf<32, 64>{H1});
     const int rc = gcm_launch_status();
     if (rc) return rc;
   }
@@ -1311,14 +1288,12 @@ extern "C" int gcm_sparse_step_cached(const float* x, const int64_t* T, const in
   }
   gcm_rows::CachedLayout lay = gcm_rows::make_cached_layout(B, N, H1, H2);
   if (!record) lay.total = 0;
-#define GCM_SC(a, b_)                                                                                         \
-  if (F == a && H1 == b_) {                                                                                   \
-    hipLaunchKernelGGL((gcm_rows::k_sparse_step_cached<a, b_>), dim3(B), dim3(64), 0, (hipStream_t)stream, x, T, \
-                       taus, E, params, weight_image, act1, act2, cache_h1, cache_agg1, cache_nodes, mx, saved,   \
-                       lay, flags, B, N, H2);                                                                     \
-    return gcm_launch_status();                                                                               \
-  }
-  GCM_SC(32, 32) GCM_SC(64, 32) GCM_SC(32, 64) GCM_SC(64, 64)
-#undef GCM_SC
-  return GCM_EUNSUPPORTED;
+  return gcm_pick(
+      [&](auto a, auto b) {
+        hipLaunchKernelGGL((gcm_rows::k_sparse_step_cached<a(), b()>), dim3(B), dim3(64), 0, (hipStream_t)stream, x, T,
+                           taus, E, params, weight_image, act1, act2, cache_h1, cache_agg1, cache_nodes, mx, saved, lay,
+                           flags, B, N, H2);
+        return gcm_launch_status();
+      },
+      OneOf<32, 64>{F}, OneOf<32, 64>{H1});
 }

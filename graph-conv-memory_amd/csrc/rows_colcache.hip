@@ -957,38 +957,22 @@ static int colcache_launch(const float* obs, const float* nodes_in, const float*
   if (!record) lay.total = 0;
   hipStream_t s = (hipStream_t)stream;
   const bool func = nodes_out != nodes_in;
-  if (F == 32 && H1 == 32 && !(has_bias & GCM_STEP_FOUR_WAVES)) {   // eight waves per graph (16-slot tiles)
-#define GCM_C8(c)                                                                                                   \
-  if ((H2 <= 32 ? 1 : 2) == c) {                                                                                    \
-    if (func)                                                                                                       \
-      hipLaunchKernelGGL((gcm_rows::k_step_colcache8<c, true>), dim3(2 * B), dim3(512), 0, s, obs,                      \
-                         nodes_in, adj_in, count_in, nodes_out, adj_out, count_out, m.ssrc, m.self, m.scol, m.sdrop,    \
-                         m.cur, m.rot, m.steady, P, cache_agg1, cache_root, saved, lay, flags, N, H2, E, B);            \
-    else                                                                                                            \
-      hipLaunchKernelGGL((gcm_rows::k_step_colcache8<c, false>), dim3(B), dim3(512), 0, s, obs, nodes_in, adj_in,       \
-                         count_in, nodes_out, adj_out, count_out, m.ssrc, m.self, m.scol, m.sdrop, m.cur, m.rot,        \
-                         m.steady, P, cache_agg1, cache_root, saved, lay, flags, N, H2, E, B);                          \
-    return gcm_launch_status();                                                                                     \
-  }
-    GCM_C8(1) GCM_C8(2)
-#undef GCM_C8
-  }
-#define GCM_CC(a, b_, c)                                                                                          \
-  if (F == a && H1 == b_ && (H2 <= 32 ? 1 : 2) == c) {                                                           \
-    if (func)                                                                                                     \
-      hipLaunchKernelGGL((gcm_rows::k_step_colcache<a, b_, c, true>), dim3((1 + GCM_STATE_WGS) * B), dim3(256), 0, s, \
-                         obs, nodes_in, adj_in, count_in, nodes_out, adj_out, count_out, m.ssrc, m.self, m.scol,      \
-                         m.sdrop, m.cur, m.rot, m.steady, P, cache_agg1, cache_root, saved, lay, flags, N, H2, E, B); \
-    else                                                                                                          \
-      hipLaunchKernelGGL((gcm_rows::k_step_colcache<a, b_, c, false>), dim3(B), dim3(256), 0, s, obs, nodes_in,       \
-                         adj_in, count_in, nodes_out, adj_out, count_out, m.ssrc, m.self, m.scol, m.sdrop, m.cur,     \
-                         m.rot, m.steady, P, cache_agg1, cache_root, saved, lay, flags, N, H2, E, B);                 \
-    return gcm_launch_status();                                                                                   \
-  }
-  GCM_CC(32, 32, 1) GCM_CC(32, 32, 2) GCM_CC(64, 32, 1) GCM_CC(64, 32, 2)
-  GCM_CC(32, 64, 1) GCM_CC(32, 64, 2) GCM_CC(64, 64, 1) GCM_CC(64, 64, 2)
-#undef GCM_CC
-  return GCM_EUNSUPPORTED;
+  auto go = [&](auto kern, int wgs, int threads) {
+    hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), 0, s, obs, nodes_in, adj_in, count_in, nodes_out, adj_out,
+                       count_out, m.ssrc, m.self, m.scol, m.sdrop, m.cur, m.rot, m.steady, P, cache_agg1, cache_root,
+                       saved, lay, flags, N, H2, E, B);
+    return gcm_launch_status();
+  };
+  const OneOf<1, 2> h2t{H2 <= 32 ? 1 : 2};
+  if (F == 32 && H1 == 32 && !(has_bias & GCM_STEP_FOUR_WAVES))   // eight waves per graph (16-slot tiles)
+    return gcm_pick(
+        [&](auto c, auto fn) { return go(gcm_rows::k_step_colcache8<c(), bool(fn())>, fn() ? 2 * B : B, 512); }, h2t,
+        Flag{func});
+  return gcm_pick(
+      [&](auto a, auto b, auto c, auto fn) {
+        return go(gcm_rows::k_step_colcache<a(), b(), c(), bool(fn())>, fn() ? (1 + GCM_STATE_WGS) * B : B, 256);
+      },
+      OneOf<32, 64>{F}, OneOf<32, 64>{H1}, h2t, Flag{func});
 }
 
 extern "C" int gcm_dense_rows_step_colcache(const float* obs, float* nodes, float* adj, int64_t* count,

@@ -707,26 +707,21 @@ extern "C" int gcm_dense_rows_step_fwd_ws(const float* obs, const float* nodes_i
   const gcm_rows::SavedLayout lay = gcm_rows::make_layout(B, N, F, H1, H2, (has_bias & GCM_GNN_RECORD_DX) != 0);
   hipStream_t s = (hipStream_t)stream;
   const int fp = F <= 32 ? 32 : 64, hp = H1 <= 32 ? 32 : 64, h2p = H2 <= 32 ? 32 : 64;
+  // nx: the node count of a tile-exact specialisation, 0 for the general kernel
+  auto go = [&](auto fp_, auto hp_, auto h2p_, auto nx) {
+    return gcm_rows::launch<fp_(), hp_(), h2p_(), nx(), nx() != 0>(s, obs, nodes_in, adj_in, count_in, nodes_out,
+                                                                    adj_out, count_out, cur_out, E, P, mx, saved, lay,
+                                                                    flags, B, N, F, H1, H2, c1, pe, sel_row);
+  };
   // tile-exact specialisations of the common shapes
-#define GCM_RX(a, n)                                                                               \
-  if (!folded && F == a && H1 == a && H2 == a && N == n)                                                      \
-    return gcm_rows::launch<a, a, a, n, true>(s, obs, nodes_in, adj_in, count_in, nodes_out,       \
-                                              adj_out, count_out, cur_out, E, P, mx, saved, lay,   \
-                                              flags, B, N, F, H1, H2);
-  GCM_RX(32, 128) GCM_RX(32, 64) GCM_RX(32, 32) GCM_RX(64, 128)
-#undef GCM_RX
+  const bool cube = !folded && F == H1 && F == H2;
+  if (cube && F == 32 && N == 128) return go(gcm_c<32>, gcm_c<32>, gcm_c<32>, gcm_c<128>);
+  if (cube && F == 32 && N == 64) return go(gcm_c<32>, gcm_c<32>, gcm_c<32>, gcm_c<64>);
+  if (cube && F == 32 && N == 32) return go(gcm_c<32>, gcm_c<32>, gcm_c<32>, gcm_c<32>);
+  if (cube && F == 64 && N == 128) return go(gcm_c<64>, gcm_c<64>, gcm_c<64>, gcm_c<128>);
   // cfg3's shape (observations of 64, hidden 32, 128 nodes), with or without a distance selector's row
   if (!c1 && !pe && F == 64 && H1 == 32 && H2 == 32 && N == 128)
-    return gcm_rows::launch<64, 32, 32, 128, true>(s, obs, nodes_in, adj_in, count_in, nodes_out, adj_out,
-                                                   count_out, cur_out, E, P, mx, saved, lay, flags, B, N, F,
-                                                   H1, H2, nullptr, nullptr, sel_row);
-#define GCM_R(a, b_, c)                                                                          \
-  if (fp == a && hp == b_ && h2p == c)                                                           \
-    return gcm_rows::launch<a, b_, c, 0, false>(s, obs, nodes_in, adj_in, count_in, nodes_out,   \
-                                                adj_out, count_out, cur_out, E, P, mx, saved,    \
-                                                lay, flags, B, N, F, H1, H2, c1, pe, sel_row);
-  GCM_R(32, 32, 32) GCM_R(32, 32, 64) GCM_R(32, 64, 32) GCM_R(32, 64, 64)
-  GCM_R(64, 32, 32) GCM_R(64, 32, 64) GCM_R(64, 64, 32) GCM_R(64, 64, 64)
-#undef GCM_R
-  return GCM_EUNSUPPORTED;
+    return go(gcm_c<64>, gcm_c<32>, gcm_c<32>, gcm_c<128>);
+  return gcm_pick([&](auto fp_, auto hp_, auto h2p_) { return go(fp_, hp_, h2p_, gcm_c<0>); }, OneOf<32, 64>{fp},
+                  OneOf<32, 64>{hp}, OneOf<32, 64>{h2p});
 }

@@ -86,14 +86,14 @@ extern "C" int gcm_skinny_wgrad(const float* dy, const float* x, float* dw_db, v
   if (O > 64 || I > 64) return GCM_EUNSUPPORTED;
   if (workspace_bytes < gcm_skinny_wgrad_workspace_bytes(M, O, I)) return GCM_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const int G = (M + ROWS - 1) / ROWS, NOT = (O + 31) / 32, NIT = (I + 31) / 32;
+  const int G = (M + ROWS - 1) / ROWS;
   float* slabs = (float*)workspace;
-#define GCM_W(a, b)                                                                           \
-  if (NOT == a && NIT == b)                                                                   \
-    hipLaunchKernelGGL((k_skinny_wgrad<a, b>), dim3(G), dim3(256), 0, s, dy, x, slabs, M, O, I);
-  GCM_W(1, 1) GCM_W(1, 2) GCM_W(2, 1) GCM_W(2, 2)
-#undef GCM_W
-  int rc = gcm_launch_status();
+  const int rc = gcm_pick(
+      [&](auto not_, auto nit) {
+        hipLaunchKernelGGL((k_skinny_wgrad<not_(), nit()>), dim3(G), dim3(256), 0, s, dy, x, slabs, M, O, I);
+        return gcm_launch_status();
+      },
+      OneOf<1, 2>{(O + 31) / 32}, OneOf<1, 2>{(I + 31) / 32});
   if (rc) return rc;
   return gcm_sum_slabs(slabs, G, O * I + O, dw_db, stream);
 }

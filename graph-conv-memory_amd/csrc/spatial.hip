@@ -286,18 +286,17 @@ int launch_count(int M, dim3 grid, size_t lds, hipStream_t st, const float* node
                  const int64_t* taus, const Cols& cols, int P, float radius, int k, int32_t* row_off,
                  uint64_t* kth, int64_t* edge_off, int N, int F, int npad) {
   const void* kern = nullptr;
-#define GCM_SPATIAL_M(MM) \
-  case MM: kern = (const void*)k_spatial_count<MODE, PC, MM>; break;
   if constexpr (MODE != GCM_SPATIAL_KNN) {
     kern = (const void*)k_spatial_count<MODE, PC, 1>;
   } else {
-    switch (M) {
-      GCM_SPATIAL_M(1) GCM_SPATIAL_M(2) GCM_SPATIAL_M(4) GCM_SPATIAL_M(8) GCM_SPATIAL_M(16)
-      GCM_SPATIAL_M(32) GCM_SPATIAL_M(64)
-      default: return GCM_EUNSUPPORTED;
-    }
+    const int rc = gcm_pick(
+        [&](auto mm) {
+          kern = (const void*)k_spatial_count<MODE, PC, mm()>;
+          return GCM_OK;
+        },
+        OneOf<1, 2, 4, 8, 16, 32, 64>{M});
+    if (rc) return rc;
   }
-#undef GCM_SPATIAL_M
   gcm_allow_dynamic_lds(kern, lds);
   void* args[] = {(void*)&nodes, (void*)&T, (void*)&taus, (void*)&cols, (void*)&P, (void*)&radius, (void*)&k,
                   (void*)&row_off, (void*)&kth, (void*)&edge_off, (void*)&N, (void*)&F, (void*)&npad};
