@@ -50,6 +50,10 @@ _CONSTANTS.update(_abi.constants(_PNA_HEADER))
 GEN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gen.h"))
 # and the section from gcm_hip_edgeconv.h (the per-edge MLP and max of EdgeConv / DenseEdgeConv and its gradients)
 EDGECONV_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_edgeconv.h"))
+# and the section from gcm_hip_mp.h (gcm.nn.MessagePassing: gather, segment reductions, segment softmax)
+_MP_HEADER = _abi.header("gcm_hip_mp.h")
+MP_PROTOTYPES = _abi.prototypes(_MP_HEADER)
+_CONSTANTS.update(_abi.constants(_MP_HEADER))
 # and the section from gcm_hip_window.h (SparseGCM.drop_oldest / reset_hidden / overflow="wrap")
 _WINDOW_HEADER = _abi.header("gcm_hip_window.h")
 WINDOW_PROTOTYPES = _abi.prototypes(_WINDOW_HEADER)
@@ -111,6 +115,7 @@ def lib():
         bind(handle, PNA_PROTOTYPES)
         bind(handle, GEN_PROTOTYPES)
         bind(handle, EDGECONV_PROTOTYPES)
+        bind(handle, MP_PROTOTYPES)
         bind(handle, WINDOW_PROTOTYPES)
         bind(handle, SEGMENT_PROTOTYPES)
         bind(handle, HEAD_PROTOTYPES)

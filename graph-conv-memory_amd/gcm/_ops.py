@@ -2018,6 +2018,168 @@ def csr_edgemax(P, Q, W2, b2, slope, graph, with_winner=False):
     return (out, winner) if with_winner else out
 
 
+# ---------------------------------------------------------------------------
+# gcm.nn.MessagePassing / gcm.graph_utils (csrc/message_passing.hip): rows gathered by an index, segments of rows
+# reduced, a softmax over the rows of a segment.  Tensors are [rows, ...] float32; the kernels see C = the product of
+# the trailing dimensions.
+# ---------------------------------------------------------------------------
+MP_OPS = {"sum": _hip.MP_SUM, "add": _hip.MP_SUM, "mean": _hip.MP_MEAN, "max": _hip.MP_MAX, "min": _hip.MP_MIN}
+
+
+class Segments:
+    """E rows grouped into M segments: `index` [E] is the segment of each row, (ptr [M+1], perm [E] | None) the list
+    per segment - position p of segment i is row perm[p], or row p when the rows are in segment order already."""
+
+    def __init__(self, index, ptr, perm, M):
+        self.index, self.ptr, self.perm, self.M = index, ptr, perm, M
+        self._inv_count = None
+
+    @property
+    def E(self):
+        return self.index.numel()
+
+    def inv_count(self):
+        """1 / max(rows of the segment, 1) [M] float32: the scale of the mean's gradient."""
+        if self._inv_count is None:
+            self._inv_count = (self.ptr[1:] - self.ptr[:-1]).clamp_(min=1).to(_f32).reciprocal_()
+        return self._inv_count
+
+    @staticmethod
+    def by_sink(graph):
+        """The segments of GraphIndex `graph` by sink, rows in the order of graph.edge_index; cached on the graph."""
+        seg = getattr(graph, "_mp_by_sink", None)
+        if seg is None:
+            seg = graph._mp_by_sink = Segments(graph.edge_index[1].contiguous(), graph.row_ptr, graph.csr_perm, graph.M)
+        return seg
+
+    @staticmethod
+    def by_source(graph):
+        """By source: the CSC view (built without a sort for SparseGCM's lists) composed with csr_perm."""
+        seg = getattr(graph, "_mp_by_source", None)
+        if seg is None:
+            col_ptr, _, perm = graph.csc()
+            if graph.csr_perm is not None:
+                perm = graph.csr_perm[perm]
+            seg = graph._mp_by_source = Segments(graph.edge_index[0].contiguous(), col_ptr, perm.contiguous(), graph.M)
+        return seg
+
+    @staticmethod
+    def from_index(index, M):
+        """Any [E] int64 index: a stable sort, as GraphIndex.from_edge_index."""
+        index = index.contiguous()
+        srt, perm = torch.sort(index, stable=True)
+        return Segments(index, ptr_from_sorted(srt, M), perm, M)
+
+
+def _mp_rows(t):
+    """(contiguous t, C) of a float32 device tensor [rows, ...]."""
+    t = t.contiguous()
+    _hip.on_device(t)
+    assert t.dtype == _f32 and t.dim() >= 1
+    return t, torch.Size(t.shape[1:]).numel()
+
+
+def _mp_gather(x, idx, scale, M):
+    x, C = _mp_rows(x)
+    out = torch.empty((idx.numel(),) + tuple(x.shape[1:]), device=x.device, dtype=_f32)
+    _call("gcm_mp_gather", _hip.ptr(x), _hip.ptr(idx), _hip.ptr(scale), _hip.ptr(out), M, idx.numel(), C,
+          _hip.stream())
+    return out
+
+
+def _mp_reduce(src, seg, op, arg=None):
+    src, C = _mp_rows(src)
+    out = torch.empty((seg.M,) + tuple(src.shape[1:]), device=src.device, dtype=_f32)
+    _call("gcm_mp_reduce", _hip.ptr(src), _hip.ptr(seg.ptr), _hip.ptr(seg.perm), op, _hip.ptr(out), _hip.ptr(arg),
+          seg.M, seg.E, C, _hip.stream())
+    return out
+
+
+class _MPGather(torch.autograd.Function):
+    """out[e] = x[seg.index[e]]; the gradient is the segment sum of g over seg.  x [M, ...]."""
+
+    @staticmethod
+    def forward(ctx, x, seg):
+        assert x.shape[0] == seg.M
+        ctx.seg = seg
+        return _mp_gather(x, seg.index, None, seg.M)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return _mp_reduce(g, ctx.seg, _hip.MP_SUM), None
+
+
+def mp_gather(x, seg):
+    return _MPGather.apply(x, seg)
+
+
+class _MPReduce(torch.autograd.Function):
+    """out[i] = op over the rows of segment i of src [E, ...]; 0 for a segment without rows.  The gradient of max /
+    min goes to the winning row alone, the first of its segment on a tie."""
+
+    @staticmethod
+    def forward(ctx, src, seg, op):
+        assert src.shape[0] == seg.E
+        arg = None
+        if op in (_hip.MP_MAX, _hip.MP_MIN) and ctx.needs_input_grad[0]:
+            arg = torch.empty((seg.M,) + tuple(src.shape[1:]), device=src.device, dtype=_i64)
+            ctx.save_for_backward(arg)
+        ctx.seg, ctx.op = seg, op
+        return _mp_reduce(src, seg, op, arg)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        seg, op = ctx.seg, ctx.op
+        if op in (_hip.MP_SUM, _hip.MP_MEAN):
+            return _mp_gather(g, seg.index, seg.inv_count() if op == _hip.MP_MEAN else None, seg.M), None, None
+        (arg,) = ctx.saved_tensors
+        g, C = _mp_rows(g)
+        g_src = torch.empty((seg.E,) + tuple(g.shape[1:]), device=g.device, dtype=_f32)
+        _call("gcm_mp_select_bwd", _hip.ptr(g), _hip.ptr(arg), _hip.ptr(seg.index), _hip.ptr(g_src), seg.M, seg.E, C,
+              _hip.stream())
+        return g_src, None, None
+
+
+def mp_reduce(src, seg, reduce):
+    return _MPReduce.apply(src, seg, MP_OPS[reduce])
+
+
+class _MPSoftmax(torch.autograd.Function):
+    """out[e] = exp(src[e]) / sum over the rows of e's segment of exp(src), per trailing element."""
+
+    @staticmethod
+    def forward(ctx, src, seg):
+        assert src.shape[0] == seg.E
+        src, C = _mp_rows(src)
+        out = torch.empty_like(src)
+        _call("gcm_mp_softmax_fwd", _hip.ptr(src), _hip.ptr(seg.ptr), _hip.ptr(seg.perm), _hip.ptr(out), seg.M, seg.E,
+              C, _hip.stream())
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(out)
+        ctx.seg = seg
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        (out,) = ctx.saved_tensors
+        seg = ctx.seg
+        g, C = _mp_rows(g)
+        g_src = torch.empty_like(out)
+        _call("gcm_mp_softmax_bwd", _hip.ptr(g), _hip.ptr(out), _hip.ptr(seg.ptr), _hip.ptr(seg.perm), _hip.ptr(g_src),
+              seg.M, seg.E, C, _hip.stream())
+        return g_src, None
+
+
+def mp_softmax(src, seg):
+    return _MPSoftmax.apply(src, seg)
+
+
 # ===========================================================================
 # LearnedEdge (edge_selectors/learned.py:53-125)
 # ===========================================================================

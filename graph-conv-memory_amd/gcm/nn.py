@@ -1324,3 +1324,9 @@ class Sequential(torch.nn.Module):
                 for k, v in zip(outs, out):
                     env[k] = v
         return out
+
+
+# the base class for layers this module does not fuse by hand, and the torch_geometric.utils functions such layers
+# are written with (imported last: they build on _ops alone)
+from .graph_utils import add_self_loops, degree, remove_self_loops, scatter, softmax  # noqa: E402,F401
+from .message_passing import MessagePassing  # noqa: E402,F401
