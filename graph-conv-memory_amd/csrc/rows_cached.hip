@@ -26,6 +26,7 @@
 #include "fused_common.h"
 #include "gcm_common.h"
 #include "rows_common.h"
+#include "rows_lean.h"
 
 #ifdef GCM_STAMPS
 __device__ unsigned long long g_stamps[32];
@@ -652,12 +653,8 @@ __device__ __forceinline__ void step_rows_cached_img_body(
     atomicOr(flags, (nonfinite ? GCM_FLAG_NONFINITE : 0u) | ((bad && !BK2) ? GCM_FLAG_BAD_COUNT : 0u));
 }
 
-// rows_cached_lean.hip: the lean form of k_step_rows_cached_img4b (cfg2's case); GCM_EUNSUPPORTED when the step does
-// not fit it (more than four source rows, the record's offsets beyond 32 bits)
-int launch_step_cached_lean(const float* obs, float* nodes, float* adj, int64_t* count, unsigned long long m0,
-                            unsigned long long m1, int self, const float* params, const float* image, float* cH,
-                            float* cA, float* cX, float* saved, const CachedLayout& lay, uint32_t* flags, int B, int N,
-                            int H2, int cur, hipStream_t stream);
+// rows_cached_lean.hip (declared in rows_lean.h): launch_step_cached_lean, the lean form of k_step_rows_cached_img4b
+// (cfg2's case); GCM_EUNSUPPORTED when the step does not fit it (the record's offsets beyond 32 bits)
 
 // The two kernels over that body.  (Separate signatures on purpose: with the decision row's pointer as a ninth
 // pointer argument of the temporal form too, the same instructions ran 170 ns per launch slower - the kernel-argument
@@ -1108,18 +1105,11 @@ extern "C" int gcm_dense_rows_step_cached_ws(const float* obs, float* nodes, flo
   if (!record) lay.total = 0;
   const gcm_rows::HopMask HM = gcm_rows::make_hop_mask(E);
   // cfg2's case (F = H1 = 32, H2 <= 32, tanh / tanh, at most four forward hops, the row known on the host): the lean
-  // kernel of rows_cached_lean.hip, its step resolved here - unless the caller asks for img4b (GCM_STEP_NOT_LEAN, A/B)
-  if (weight_image && !sel_row && (has_bias & GCM_STEP_IMG_V4) && !(has_bias & (GCM_STEP_ONE_WAVE | GCM_STEP_NOT_LEAN)) &&
-      F == 32 && H1 == 32 && H2 <= 32 && act1 == GCM_ACT_TANH && act2 == GCM_ACT_TANH && HM.n4 >= 0 && cur_host >= 0 &&
-      cur_host < N) {
-    unsigned long long m0 = 0ull, m1 = 0ull;   // the sources of row cur: j = cur - h for the hops 0 < h < 128
-    for (int i = 0; i < E.n_hops; ++i) {
-      const int h = E.hops[i], j = cur_host - h;
-      if (h <= 0 || h >= 128 || j < 0) continue;
-      if (j < 64) m0 |= 1ull << j;
-      else m1 |= 1ull << (j - 64);
-    }
-    const int rc = gcm_rows::launch_step_cached_lean(obs, nodes, adj, count, m0, m1, HM.self, params, weight_image,
+  // kernel of rows_cached_lean.hip, its step resolved here - unless the caller asks for img4b (GCM_STEP_NOT_LEAN, A/B);
+  // the decision is gcm_rows::lean_step_case, which the run entry (rows_cached_run.hip) takes too
+  gcm_rows::LeanCase lc;
+  if (gcm_rows::lean_step_case(selectors, n_selectors, weight_image, has_bias, act1, act2, N, F, H1, H2, cur_host, lc)) {
+    const int rc = gcm_rows::launch_step_cached_lean(obs, nodes, adj, count, lc.m0, lc.m1, lc.self, params, weight_image,
                                                      cache_h1, cache_agg1, cache_nodes, saved, lay, flags, B, N, H2,
                                                      cur_host, (hipStream_t)stream);
     if (rc != GCM_EUNSUPPORTED) return rc;

@@ -20,21 +20,9 @@
 #include "fused_common.h"
 #include "gcm_common.h"
 #include "rows_common.h"
+#include "rows_lean.h"
 
 namespace gcm_rows {
-
-// a half-wave's sixteen k of a layer's two products (image3 pairs, sv = (agg, x)[k] pairs), two chains of eight
-__device__ __forceinline__ float lean_half_matvec(const f32x2 (&w)[16], const float* sv, int kh) {
-  f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const f32x4 u = *reinterpret_cast<const f32x4*>(sv + 32 * kh + 4 * j);
-    acc0 = w[2 * j] * f32x2{u[0], u[1]} + acc0;
-    acc1 = w[2 * j + 1] * f32x2{u[2], u[3]} + acc1;
-  }
-  const f32x2 acc = acc0 + acc1;
-  return gcm_xor32_add(acc[0] + acc[1]);
-}
 
 // src4: the source rows of row cur, ascending, one byte each, 0xff for an empty slot.  nhs: N | H2 << 8 | self << 16.
 // m0, m1: the source rows as a mask (without the self loop); o_*: the record's float offsets (CachedLayout), rec = 0:
@@ -164,5 +152,7 @@ int launch_step_cached_lean(const float* obs, float* nodes, float* adj, int64_t*
                      (unsigned)lay.o_coef, (unsigned)lay.o_live, lay.total ? 1 : 0);
   return gcm_launch_status();
 }
+
+const void* lean_step_kernel() { return (const void*)k_step_rows_cached_img4_lean; }
 
 }  // namespace gcm_rows

@@ -54,6 +54,8 @@ struct StepCfg {
   int cached_flags = 0;   // extra has_bias bits of the cached step only (GCM_STEP_TWO_LAUNCH: the A/B of tests / tools)
   bool col_cache = true;  // chains whose selectors write column cur take gcm_dense_rows_step_colcache (A/B switch)
   bool hops_bptt = true;  // forward-hop cached chains take gcm_dense_rows_bptt_cached_hops in their backward (A/B switch)
+  bool merge_captured = true;   // lean cached steps captured back to back become one graph node (A/B switch)
+  int merge_cap = 0;            // steps per such node (tests split a run with it); 0: the library's cap
   int64_t P;
   bool has_distance = false;
   at::Tensor ws;   // scratch of the distance selectors
@@ -618,14 +620,17 @@ struct RecordPool {
   int64_t rec_size = 0, rec_used = 0;
   void* rec_stream = nullptr;
   unsigned long long rec_capture = 0;
+  int capturing = -1;   // what the last take() saw of its stream: 1 being captured, 0 not, -1 it did not look
   static constexpr int64_t REC_PER_BLOCK = 16;
   at::Tensor take(int64_t floats, const at::Tensor& like, int dev) {
     const int64_t n = pad64(floats);
+    capturing = -1;
     if (n * (int64_t)sizeof(float) > (1 << 20)) return at::empty({n}, like.options());   // (large records: their own allocation)
     hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     unsigned long long cid = 0;
     if (hipStreamGetCaptureInfo(st, &cs, &cid) != hipSuccess || cs != hipStreamCaptureStatusActive) cid = 0;
+    capturing = cid != 0 ? 1 : 0;
     if (!rec_block.defined() || rec_size != n || rec_used == REC_PER_BLOCK || rec_stream != (void*)st || rec_capture != cid) {
       rec_block = at::empty({REC_PER_BLOCK * n}, like.options());
       rec_size = n;
@@ -699,6 +704,10 @@ struct RowsFast {
            l_count._version() == lv_count;
   }
   int dev = -1;
+  // the chain's run object (gcm_hip_run.h): inside a stream capture, cached lean steps that follow one another directly
+  // are appended to ONE graph node.  Reset whenever the chain is re-armed or a step comes through the checked entry.
+  void* mrun = nullptr;
+  int mrun_cap = 0;
 
   RowsFast(const std::vector<std::pair<pybind11::object, pybind11::object>>& specs,
            const std::vector<pybind11::object>& hooks)
@@ -707,6 +716,31 @@ struct RowsFast {
       dicts.push_back(s.first);
       keys.push_back(s.second);
     }
+  }
+  RowsFast(const RowsFast&) = delete;
+  RowsFast& operator=(const RowsFast&) = delete;
+  ~RowsFast() {
+    if (mrun) gcm_rows_run_destroy(mrun);
+  }
+  bool last_cached_eager = true;   // the last cached step ran outside a capture: merge_stats() is then {0, 0}
+  // nullptr: the switch is off, or the record pool has just seen that the stream is not being captured - the step is
+  // then gcm_dense_rows_step_cached_ws exactly, without a second look at the stream (a capture query is ~1 us of host
+  // time, a fifth of an eager step)
+  void* merge_run() {
+    last_cached_eager = rec_pool.capturing == 0;
+    if (!cfg->merge_captured || rec_pool.capturing == 0) return nullptr;
+    if (!mrun) mrun = gcm_rows_run_create();
+    const int cap = cfg->merge_cap > 0 ? std::min(cfg->merge_cap, gcm_rows_run_steps_cap()) : gcm_rows_run_steps_cap();
+    if (mrun && cap != mrun_cap) {
+      gcm_rows_run_set_cap(mrun, cap);
+      mrun_cap = cap;
+    }
+    return mrun;
+  }
+  std::pair<int, int> merge_stats() const {
+    int out[2] = {0, 0};
+    if (mrun && !last_cached_eager) gcm_rows_run_stats(mrun, out);
+    return {out[0], out[1]};
   }
 
   bool hooks_registered() const {   // torch.nn.Module.__call__ has work to do: take the long way
@@ -800,6 +834,7 @@ struct RowsFast {
     }
     chain_steps = cached_steps = rolled_steps = col_steps = 0;
     cH = cA = cX = rH = rA = rX = abits = kA = kR = at::Tensor();
+    if (mrun) gcm_rows_run_reset(mrun);
     // (a distance selector's decisions reach the cached step as a row: no hop table to rebuild the live rows from
     //  in the observation-gradient launch - those chains stay on the general kernel)
     cache_ok = fresh && donate && dx_kind != 2 && !(cfg->has_distance && dx_kind != 0) &&
@@ -1021,16 +1056,17 @@ struct RowsFast {
                                           reinterpret_cast<uint32_t*>(abits.data_ptr()),
                                           reinterpret_cast<uint32_t*>(flags.data_ptr()), (int)B, N, F, H1, H2, stream),
             "gcm_edge_distance_step_cached");
-    } else
-    check(gcm_dense_rows_step_cached_ws(obs.data_ptr<float>(), nodes_in.data_ptr<float>(), adj_in.data_ptr<float>(),
-                                        count_in.data_ptr<int64_t>(), cfg->descs.empty() ? nullptr : cfg->descs.data(),
-                                        (int)cfg->descs.size(), packed.data_ptr<float>(), wimg.data_ptr<float>(),
-                                        cfg->has_bias | cfg->cached_flags,
-                                        cfg->act1, cfg->act2, cH.data_ptr<float>(), cA.data_ptr<float>(), cX.data_ptr<float>(),
-                                        buf.data_ptr<float>(), need_bwd ? 1 : 0, (int)cached_steps,
-                                        reinterpret_cast<uint32_t*>(flags.data_ptr()), ws, ws_bytes, (int)B, N, F, H1, H2,
-                                        stream),
-          "gcm_dense_rows_step_cached_ws");
+    } else   // (with the chain's run object: captured back to back, lean steps share one graph node - gcm_hip_run.h)
+    check(gcm_dense_rows_step_cached_run(merge_run(), obs.data_ptr<float>(), nodes_in.data_ptr<float>(),
+                                         adj_in.data_ptr<float>(), count_in.data_ptr<int64_t>(),
+                                         cfg->descs.empty() ? nullptr : cfg->descs.data(), (int)cfg->descs.size(),
+                                         packed.data_ptr<float>(), wimg.data_ptr<float>(),
+                                         cfg->has_bias | cfg->cached_flags, cfg->act1, cfg->act2, cH.data_ptr<float>(),
+                                         cA.data_ptr<float>(), cX.data_ptr<float>(), buf.data_ptr<float>(),
+                                         need_bwd ? 1 : 0, (int)cached_steps,
+                                         reinterpret_cast<uint32_t*>(flags.data_ptr()), ws, ws_bytes, (int)B, N, F, H1,
+                                         H2, stream),
+          "gcm_dense_rows_step_cached_run");
     PROF_T(2)
     at::Tensor mx = alias_of(buf, 0, {B, H2}, buf.dtype());
     PROF_T(3)
@@ -1191,6 +1227,7 @@ struct RowsFast {
       arm(packed_, flags_, cfg_handle, donate_, need_dx, nodes_in, count_in, fresh);
     else if ((cache_ok || col_ok) && !continues(nodes_in, adj_in, weights, count_in))
       cache_ok = col_ok = false;
+    if (mrun) gcm_rows_run_reset(mrun);   // (only the unchecked entry, which knows the chain continues, appends to a node)
     at::Tensor mx = launch(obs, nodes_in, adj_in, weights, count_in);
     return pybind11::make_tuple(mx, l_nodes, l_adj, l_count, donate);
   }
@@ -2860,6 +2897,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_cached_flags", [](StepCfg& c, int f) { c.cached_flags = f; })
       .def("set_hops_bptt", [](StepCfg& c, bool on) { c.hops_bptt = on; })
       .def("set_col_cache", [](StepCfg& c, bool on) { c.col_cache = on; })
+      .def("set_merge_captured", [](StepCfg& c, bool on, int cap) { c.merge_captured = on; c.merge_cap = cap; })
       .def("cached_launches", [](StepCfg& c, int B) {   // launches per cached step (0: no cached form)
         return gcm_dense_rows_cached_launches(c.descs.empty() ? nullptr : c.descs.data(), (int)c.descs.size(),
                                               c.has_bias | c.cached_flags, B, c.N, c.F, c.H1, c.H2);
@@ -2880,6 +2918,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("cached_steps", [](RowsFast& f) { return f.cached_steps - f.col_steps; })
       .def("rolled_steps", [](RowsFast& f) { return f.rolled_steps; })
       .def("col_steps", [](RowsFast& f) { return f.col_steps; })
+      .def("merge_stats", &RowsFast::merge_stats)
       .def("has_chain", [](RowsFast& f) { return f.node != nullptr || f.dxc != nullptr; });
   pybind11::class_<LearnedCfg>(m, "LearnedCfg")
       .def(pybind11::init<int, int, int, int, int, int, int, double, double, double>())

@@ -179,6 +179,13 @@ class DenseGCM(torch.nn.Module):
         # fp32 on the current HIP device, and nothing is folded into the vector.  False (env GCM_FUSED_HEAD=0): the three
         # launches (A/B); the same bits either way
         self.rows_fused_head = os.environ.get("GCM_FUSED_HEAD", "1") == "1"
+        # True: while a HIP graph is being captured, lean cached steps that follow one another directly - the stream's only
+        # pending dependency is the node the previous step became, and the step continues that chain - are appended to
+        # that node (csrc/rows_cached_run.hip: k_step_rows_cached_img4_lean_run makes them back to back in one launch)
+        # instead of becoming ~1.6 us graph nodes of their own.  Eager steps are untouched.  False (env
+        # GCM_MERGE_CAPTURED=0): one node per step (A/B); the same bits either way.  Read when a chain is armed
+        self.rows_merge_captured = os.environ.get("GCM_MERGE_CAPTURED", "1") == "1"
+        self.rows_merge_cap = None   # tests: steps per merged node (None: the library's cap)
         self._head_ready = None   # (cfg, grad mode) of the packed vector forward(x, None) has just built with the state
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
@@ -229,6 +236,17 @@ class DenseGCM(torch.nn.Module):
             if cfg is not False and cfg._rows_fast is not None:
                 n += cfg._rows_fast.steps()
         return n
+
+    def merge_stats(self):
+        """What became of this module's cached steps in the stream capture seen last: {"nodes": graph nodes they were
+        launched as, "merged_steps": steps appended to an existing node instead (rows_merge_captured)}.  Both 0 after
+        an eager step."""
+        nodes = merged = 0
+        for cfg in self._cfg_cache.values():
+            if cfg is not False and cfg._rows_fast is not None:
+                a, b = cfg._rows_fast.merge_stats()
+                nodes, merged = nodes + a, merged + b
+        return {"nodes": nodes, "merged_steps": merged}
 
     def learned_fast_steps(self):
         """Number of LearnedEdge steps that went from __call__ straight into the C++ host path (LearnedFast)."""
@@ -737,6 +755,7 @@ class DenseGCM(torch.nn.Module):
                     | (0 if self.rows_lean_step else _hip.STEP_NOT_LEAN))
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
                 cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
+                cfg._cpp.set_merge_captured(bool(self.rows_merge_captured), int(self.rows_merge_cap or 0))
             image = self._packed_cache[5]
             if image is not None and self._packed_cache[1] is root:
                 fast.set_head_image(root, image)   # (the first cached step takes it iff it is armed with this vector)

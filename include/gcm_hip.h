@@ -821,6 +821,10 @@ int gcm_dense_rows_step_cached_ws(const float* obs, float* nodes, float* adj, in
                                   float* cache_agg1, float* cache_nodes, float* saved, int record, int cur_host,
                                   uint32_t* flags, void* workspace, size_t workspace_bytes, int B, int N, int F,
                                   int H1, int H2, gcm_stream_t stream);
+/* ... and the same entry with a per-chain run object: inside a stream capture, lean steps that follow one another
+ * directly become ONE graph node that runs them back to back (csrc/rows_cached_run.hip).
+ * Declared in gcm_hip_run.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_run.h"
 /* EuclideanEdge (distance.py:41-49, not bidirectional) as the ONLY selector of such a chain: the distance kernel and
  * the cached step as one launch (the step is the tail of the matrix-core distance kernel's first wave) -
  * gcm_dense_rows_step_cached_ws takes this path by itself when the shapes allow (>= 32 current rows, F in {32, 64},
