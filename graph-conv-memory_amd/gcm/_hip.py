@@ -54,6 +54,10 @@ EDGECONV_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_edgeconv.h"))
 _MP_HEADER = _abi.header("gcm_hip_mp.h")
 MP_PROTOTYPES = _abi.prototypes(_MP_HEADER)
 _CONSTANTS.update(_abi.constants(_MP_HEADER))
+# and the section from gcm_hip_bridge.h (gcm.gcm.DenseToSparse / SparseToDense: adjacency <-> edge list and index)
+_BRIDGE_HEADER = _abi.header("gcm_hip_bridge.h")
+BRIDGE_PROTOTYPES = _abi.prototypes(_BRIDGE_HEADER)
+_CONSTANTS.update(_abi.constants(_BRIDGE_HEADER))
 # and the section from gcm_hip_window.h (SparseGCM.drop_oldest / reset_hidden / overflow="wrap")
 _WINDOW_HEADER = _abi.header("gcm_hip_window.h")
 WINDOW_PROTOTYPES = _abi.prototypes(_WINDOW_HEADER)
@@ -118,6 +122,7 @@ def lib():
         bind(handle, GEN_PROTOTYPES)
         bind(handle, EDGECONV_PROTOTYPES)
         bind(handle, MP_PROTOTYPES)
+        bind(handle, BRIDGE_PROTOTYPES)
         bind(handle, WINDOW_PROTOTYPES)
         bind(handle, SEGMENT_PROTOTYPES)
         bind(handle, HEAD_PROTOTYPES)

@@ -463,16 +463,19 @@ class GraphIndex:
     built lazily, CSC by source (backward gather).  Attached to the edge_index tensor handed
     to the GNN (attribute `gcm_graph`) so GraphConv layers share it."""
 
-    def __init__(self, edge_index, row_ptr, M, csr_perm=None, mask=None, batches=None):
+    def __init__(self, edge_index, row_ptr, M, csr_perm=None, mask=None, batches=None, col=None, csc=None):
         self.edge_index = edge_index            # [2, E] (source, sink); CSR order unless csr_perm
         self.csr_perm = csr_perm                # positions of the CSR entries in edge_index
         self.row_ptr, self.M, self.mask = row_ptr, M, mask
         # (node_off [B+1], B, max nodes per graph) when the list is grouped by graph and no edge
         # leaves its graph (SparseGCM's flat list): the CSC view is then built without a sort
         self.batches = batches
-        src = edge_index[0] if csr_perm is None else edge_index[0][csr_perm]
-        self.col = src.contiguous()
-        self._csc = None
+        # col: the sources in CSR order, csc: the (col_ptr, rows, perm) of csc(), when the builder of the list has
+        # them already (DenseToSparse: both orders of a dense adjacency come out of one pass)
+        if col is None:
+            col = edge_index[0] if csr_perm is None else edge_index[0][csr_perm]
+        self.col = col.contiguous()
+        self._csc = csc
 
     @property
     def E(self):
@@ -2178,6 +2181,170 @@ class _MPSoftmax(torch.autograd.Function):
 
 def mp_softmax(src, seg):
     return _MPSoftmax.apply(src, seg)
+
+
+# ===========================================================================
+# The dense <-> sparse bridge (gcm.gcm.DenseToSparse / SparseToDense; csrc/dense_sparse.hip, gcm_hip_bridge.h)
+# ===========================================================================
+BRIDGE_MAX_N = _hip.BRIDGE_MAX_N
+_node_off_cache = {}
+
+
+def _node_off(B, N, device):
+    """[0, N, 2N, ..., B*N] on the device (GraphIndex.batches of a padded batch); kept per shape."""
+    key = (B, N, device)
+    off = _node_off_cache.get(key)
+    if off is None:
+        if len(_node_off_cache) >= 16:
+            _node_off_cache.clear()
+        off = _node_off_cache[key] = torch.arange(0, B * N + 1, N, dtype=_i64, device=device)
+    return off
+
+
+def dense_to_sparse(adj, transpose, with_values):
+    """adj [B,N,N] (float32 or int64, N <= BRIDGE_MAX_N) -> (edge_index [2,E], GraphIndex, values [E] | None): the
+    entries > 0 in (b, r, c) order as (b*N + r, b*N + c) - swapped with `transpose` - and their index by sink and by
+    source, built by counting (no sort).  Three launches and ONE host read, of E; not differentiable (the caller
+    wraps the values)."""
+    adj = adj.contiguous()
+    _hip.on_device(adj)
+    assert adj.dim() == 3 and adj.shape[1] == adj.shape[2] and adj.dtype in (_f32, _i64)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("DenseToSparse reads the number of edges back to the host to size the edge list, which "
+                           "a stream capture cannot do: run it outside torch.cuda.graph(...)")
+    B, N = adj.shape[0], adj.shape[1]
+    M, W, dev, st = B * N, (N + 63) // 64, adj.device, _hip.stream()
+    is_i64 = int(adj.dtype == _i64)
+    image = torch.empty(M * W, dtype=_i64, device=dev)
+    counts = torch.empty(2 * M + B, dtype=torch.int32, device=dev)      # row counts | column counts | graph totals
+    row_cnt, col_cnt, total = counts[:M], counts[M:2 * M], counts[2 * M:]
+    graph_off = torch.empty(B + 1, dtype=_i64, device=dev)
+    _call("gcm_bridge_image", _hip.ptr(adj), is_i64, _hip.ptr(image), _hip.ptr(row_cnt), _hip.ptr(col_cnt),
+          _hip.ptr(total), B, N, st)
+    _call("gcm_bridge_scan", _hip.ptr(total), _hip.ptr(graph_off), B, st)
+    E = int(graph_off[B])                                               # the host read
+    edge_index = torch.empty(2, E, dtype=_i64, device=dev)
+    ptrs = torch.empty(2, M + 1, dtype=_i64, device=dev)
+    by_col = torch.empty(E, dtype=_i64, device=dev)
+    col_rows = torch.empty(E, dtype=_i64, device=dev)
+    col_pos = None if transpose else torch.empty(E, dtype=_i64, device=dev)
+    values = torch.empty(E, dtype=_f32, device=dev) if with_values else None
+    _call("gcm_bridge_fill", _hip.ptr(adj), is_i64, _hip.ptr(image), _hip.ptr(row_cnt), _hip.ptr(col_cnt),
+          _hip.ptr(graph_off), _hip.ptr(edge_index), _hip.ptr(ptrs[0]), _hip.ptr(ptrs[1]), _hip.ptr(by_col),
+          _hip.ptr(col_pos), _hip.ptr(col_rows), _hip.ptr(values), B, N, E, int(transpose), st)
+    batches = (_node_off(B, N, dev), B, N)
+    if transpose:   # the row is the sink: the list is in CSR order already, the column-major order is its CSC
+        graph = GraphIndex(edge_index, ptrs[0], M, batches=batches, col=edge_index[0],
+                           csc=(ptrs[1], col_rows, by_col))
+    else:           # the row is the source: the column-major order is the CSR, the list order its CSC
+        graph = GraphIndex(edge_index, ptrs[1], M, csr_perm=by_col, batches=batches, col=col_rows,
+                           csc=(ptrs[0], edge_index[1], col_pos))
+    return edge_index, graph, values
+
+
+class _BridgeValues(torch.autograd.Function):
+    """DenseToSparse with edge values: values[e] = adj[b, r, c] of edge e, differentiable in adj (the gradient is
+    scattered into a zero [B,N,N]); `out` receives (edge_index, graph)."""
+
+    @staticmethod
+    def forward(ctx, adj, transpose, out):
+        edge_index, graph, values = dense_to_sparse(adj, transpose, True)
+        out.extend((edge_index, graph))
+        ctx.edge_index, ctx.transpose, ctx.dims = edge_index, transpose, adj.shape[:2]
+        return values
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        B, N = ctx.dims
+        g = g.contiguous()
+        g_adj = torch.empty(B, N, N, dtype=_f32, device=g.device)
+        _call("gcm_bridge_values_bwd", _hip.ptr(g), _hip.ptr(ctx.edge_index), _hip.ptr(g_adj), B, N, g.numel(),
+              int(ctx.transpose), _hip.stream())
+        return g_adj, None, None
+
+
+def dense_to_sparse_values(adj, transpose):
+    """-> (edge_index, graph, values) with values differentiable in a float32 adj."""
+    if adj.dtype != _f32:
+        return dense_to_sparse(adj, transpose, True)
+    out = []
+    values = _BridgeValues.apply(adj, transpose, out)
+    return out[0], out[1], values
+
+
+class _BridgeDenseNodes(torch.autograd.Function):
+    """x [B,N,F] from x_sp [M,F]: node m at (its graph, m - first node of the graph), positions >= N dropped, the rest 0."""
+
+    @staticmethod
+    def forward(ctx, x_sp, batch_idx, node_ptr, B, N):
+        x_sp = x_sp.contiguous()
+        M, F = x_sp.shape
+        x = torch.empty(B, N, F, dtype=_f32, device=x_sp.device)
+        _call("gcm_bridge_dense_nodes", _hip.ptr(x_sp), _hip.ptr(node_ptr), _hip.ptr(x), M, B, N, F, _hip.stream())
+        ctx.save_for_backward(batch_idx, node_ptr)
+        ctx.dims = (M, B, N, F)
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        batch_idx, node_ptr = ctx.saved_tensors
+        M, B, N, F = ctx.dims
+        g = g.contiguous()
+        g_sp = torch.empty(M, F, dtype=_f32, device=g.device)
+        _call("gcm_bridge_dense_nodes_bwd", _hip.ptr(g), _hip.ptr(batch_idx), _hip.ptr(node_ptr), _hip.ptr(g_sp), M, B,
+              N, F, _hip.stream())
+        return g_sp, None, None, None, None
+
+
+class _BridgeDenseAdj(torch.autograd.Function):
+    """adj [B,N,N]: adj[b, s, d] += weight (or 1) per edge, summed per sink in CSR order; the gradient of the weights
+    is a gather."""
+
+    @staticmethod
+    def forward(ctx, edge_weight, graph, batch_idx, node_ptr, B, N):
+        dev = batch_idx.device
+        adj = torch.empty(B, N, N, dtype=_f32, device=dev)
+        _call("gcm_bridge_dense_adj", _hip.ptr(graph.row_ptr), _hip.ptr(graph.csr_perm), _hip.ptr(graph.edge_index),
+              _hip.ptr(edge_weight), _hip.ptr(batch_idx), _hip.ptr(node_ptr), _hip.ptr(adj), graph.M, graph.E, B, N,
+              _hip.stream())
+        ctx.save_for_backward(batch_idx, node_ptr)
+        ctx.graph, ctx.dims = graph, (B, N)
+        return adj
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        batch_idx, node_ptr = ctx.saved_tensors
+        graph, (B, N) = ctx.graph, ctx.dims
+        g = g.contiguous()
+        g_w = torch.empty(graph.E, dtype=_f32, device=g.device)
+        _call("gcm_bridge_dense_adj_bwd", _hip.ptr(g), _hip.ptr(graph.edge_index), _hip.ptr(batch_idx),
+              _hip.ptr(node_ptr), _hip.ptr(g_w), graph.M, graph.E, B, N, _hip.stream())
+        return g_w, None, None, None, None, None
+
+
+def sparse_to_dense(x_sp, graph, batch_idx, B, N, edge_weight=None):
+    """(x [B,N,F], adj [B,N,N]) of flat nodes x_sp [M,F] float32, their non-decreasing graph ids batch_idx [M] and
+    the edges of `graph` (a GraphIndex over the M nodes)."""
+    batch_idx = batch_idx.contiguous()
+    edge_index = graph.edge_index.contiguous()
+    if edge_weight is not None:
+        edge_weight = edge_weight.contiguous()
+        assert edge_weight.dtype == _f32 and edge_weight.numel() == graph.E
+    _hip.on_device(x_sp.contiguous(), batch_idx, edge_index, edge_weight)
+    assert x_sp.dim() == 2 and x_sp.dtype == _f32 and batch_idx.dtype == _i64 and batch_idx.numel() == x_sp.shape[0]
+    assert graph.M == x_sp.shape[0] and x_sp.shape[1] > 0
+    if edge_index is not graph.edge_index:      # (a strided list: the kernels read [2,E] rows)
+        graph = GraphIndex(edge_index, graph.row_ptr, graph.M, csr_perm=graph.csr_perm, col=graph.col)
+    node_ptr = ptr_from_sorted(batch_idx, B)
+    x = _BridgeDenseNodes.apply(x_sp, batch_idx, node_ptr, B, N)
+    adj = _BridgeDenseAdj.apply(edge_weight, graph, batch_idx, node_ptr, B, N)
+    return x, adj
 
 
 # ===========================================================================

@@ -27,6 +27,126 @@ from . import _hip, _ops
 _DTYPES = (torch.float32, torch.float32, torch.float32, torch.float32, torch.int64, 1)
 
 
+class SparseToDense(torch.nn.Module):
+    """Edge list back to a padded batch (reference: src/gcm/gcm.py:10-21; PyG's to_dense_batch / to_dense_adj with
+    max_num_nodes=N).
+
+        x [B,N,F], adj [B,N,N] float32 = SparseToDense()(x_sp [M,F], edge_index [2,E], batch_idx [M], B, N,
+                                                         edge_weight=None)
+
+    batch_idx is non-decreasing.  Node m lands at (batch_idx[m], m - first node of its graph); positions >= N are
+    dropped and rows no node fills are 0.  adj[b, source, sink] += 1 per edge - += edge_weight[e] when given - so
+    duplicate edges add; an edge with an end beyond N, or with its ends in two graphs, is dropped.  On a HIP device
+    both are kernels (csrc/dense_sparse.hip): every sink sums its edges in the order of its CSR entries - the index
+    attached to edge_index as `gcm_graph` when there is one, else one built here - so results are bitwise
+    reproducible, without float atomics.  Gradients reach x_sp and edge_weight.
+
+    Two deliberate differences from the reference: the batch size is the argument B (the reference reads
+    batch_idx.max() + 1 back to the host), and adj is the whole [B,N,N] (the reference returns to_dense_adj(...)[0],
+    the first graph's [N,N] only, which its test cannot tell apart because all its graphs are equal)."""
+
+    def forward(self, x, edge_index, batch_idx, B, N, edge_weight=None):
+        B, N = int(B), int(N)
+        if x.dim() != 2 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+            raise ValueError("SparseToDense takes x [M,F] and edge_index [2,E]")
+        if edge_weight is not None and edge_weight.numel() != edge_index.shape[1]:
+            raise ValueError("edge_weight must hold one value per edge")
+        M, F = x.shape
+        if not x.is_cuda or F == 0:
+            return self._torch_forward(x, edge_index, batch_idx, B, N, edge_weight)
+        with torch.cuda.device(x.device):
+            graph = getattr(edge_index, "gcm_graph", None)
+            if graph is None or graph.M != M or graph.mask is not None:
+                graph = _ops.GraphIndex.from_edge_index(edge_index, M)
+            if edge_weight is not None:
+                edge_weight = edge_weight.to(torch.float32).view(-1)
+            return _ops.sparse_to_dense(x.to(torch.float32), graph, batch_idx.to(torch.int64), B, N, edge_weight)
+
+    @staticmethod
+    def _torch_forward(x, edge_index, batch_idx, B, N, edge_weight):
+        """The same function in torch ops (CPU tensors): index_put with accumulate, which a CPU runs in list order."""
+        M = x.shape[0]
+        batch_idx = batch_idx.to(torch.int64)
+        first = torch.searchsorted(batch_idx, torch.arange(B, device=x.device))
+        inside = (batch_idx >= 0) & (batch_idx < B)
+        graph = batch_idx.clamp(0, max(B - 1, 0))
+        pos = torch.arange(M, device=x.device) - first[graph]
+        keep = inside & (pos >= 0) & (pos < N)
+        dense = x.new_zeros(B, N, x.shape[1]).index_put((graph[keep], pos[keep]), x[keep])
+        src, dst = edge_index[0], edge_index[1]
+        ends = (src >= 0) & (src < M) & (dst >= 0) & (dst < M)
+        src, dst = src.clamp(0, max(M - 1, 0)), dst.clamp(0, max(M - 1, 0))
+        ok = ends & keep[src] & keep[dst] & (graph[src] == graph[dst])
+        w = torch.ones(src.numel(), device=x.device) if edge_weight is None else edge_weight.to(torch.float32).view(-1)
+        adj = torch.zeros(B, N, N, device=x.device).index_put((graph[src][ok], pos[src][ok], pos[dst][ok]), w[ok],
+                                                              accumulate=True)
+        return dense, adj
+
+
+class DenseToSparse(torch.nn.Module):
+    """Padded batch to an edge list (reference: src/gcm/gcm.py:24-53), so that sparse `edge_index` layers - the fused
+    ones of gcm.nn and any gcm.nn.MessagePassing subclass - run inside DenseGCM behind its selectors.
+
+        x_sp [B*N,F], edge_index [2,E] int64, batch_idx [B*N] int64 = DenseToSparse()(x [B,N,F], adj [B,N,N])
+        ..., edge_weight [E] float32                                = DenseToSparse(edge_values=True)(x, adj)
+
+    The edges are the entries adj[b,r,c] > 0 (strictly: a negative entry is no edge), in (b, r, c) order, which is
+    torch.nonzero's.  x_sp is a view of x; mask must be None (the reference raises NotImplementedError too).
+
+    ORIENTATION.  The reference emits (b*N + r, b*N + c): the ROW is the source.  The dense layers, and every
+    selector of DenseGCM, read adj[b,i,j] as "i aggregates from j": the row is the sink.  Through the reference's
+    bridge a sparse layer therefore works on the TRANSPOSED graph.  transpose=False (default) reproduces the
+    reference; transpose=True emits (b*N + c, b*N + r) in the same list order, and a sparse layer then aggregates
+    exactly as its dense twin does on the same adj.  Use transpose=True behind DenseGCM's selectors.
+
+    edge_values=True also returns the values adj[b,r,c] of the edges, differentiable in adj (the gradient is scattered
+    into a zero [B,N,N]): what the reference's docstring promises and its code does not do.
+
+    On a HIP device with N <= 512 (GCM_BRIDGE_MAX_N: one thread per column of a graph) this is three kernels of
+    csrc/dense_sparse.hip and ONE host read, of E.  float32 and int64 adj are read as they are, other dtypes are
+    converted first.  The GraphIndex of the list (M = B*N; CSR by sink, the CSC view, batches) is attached as
+    `edge_index.gcm_graph` - the arrays GraphIndex.from_edge_index and its csc() would compute, built by counting
+    instead of two device-wide sorts - so the layers behind the bridge index nothing.  Inside a stream capture the host
+    read is impossible and the call raises RuntimeError.  CPU tensors and larger N take torch ops (nonzero); on a
+    device the index is then built by from_edge_index."""
+
+    def __init__(self, transpose=False, edge_values=False):
+        super().__init__()
+        self.transpose, self.edge_values = bool(transpose), bool(edge_values)
+
+    def extra_repr(self):
+        return f"transpose={self.transpose}, edge_values={self.edge_values}"
+
+    def forward(self, x, adj, mask=None):
+        assert x.dim() == adj.dim() == 3
+        if mask is not None:
+            raise NotImplementedError("DenseToSparse: mask is not supported (nor is it in the reference)")
+        B, N = x.shape[0], x.shape[1]
+        assert adj.shape == (B, N, N), "adj must be [B,N,N] over the nodes of x"
+        x_sp = x.view(B * N, x.shape[-1]) if x.is_contiguous() else x.reshape(B * N, x.shape[-1])
+        if adj.is_cuda and 1 <= N <= _ops.BRIDGE_MAX_N and B >= 1:
+            if adj.dtype not in (torch.float32, torch.int64):
+                adj = adj.to(torch.float32)     # (autograd's own op: a gradient still reaches the caller's adj)
+            with torch.cuda.device(adj.device):
+                if self.edge_values:
+                    edge_index, graph, values = _ops.dense_to_sparse_values(adj, self.transpose)
+                else:
+                    edge_index, graph, values = _ops.dense_to_sparse(adj, self.transpose, False)
+                batch_idx = torch.arange(B * N, device=adj.device) // N
+        else:
+            b, r, c = torch.nonzero(adj > 0).t()
+            rows, cols = b * N + r, b * N + c
+            edge_index = torch.stack([cols, rows] if self.transpose else [rows, cols], dim=0).long()
+            values = adj[b, r, c].to(torch.float32) if self.edge_values else None
+            batch_idx = torch.arange(B, device=x.device).view(-1, 1).repeat(1, N).view(-1)
+            graph = _ops.GraphIndex.from_edge_index(edge_index, B * N) if adj.is_cuda else None
+        if graph is not None:
+            edge_index.gcm_graph = graph
+        if self.edge_values:
+            return x_sp, edge_index, batch_idx, values
+        return x_sp, edge_index, batch_idx
+
+
 class PositionalEncoding(torch.nn.Module):
     """Embed a sin/cos positional encoding into the graph without touching future nodes
     (node index > num_nodes).  Reference: src/gcm/gcm.py:92-143 (same constructor, same lazily

@@ -1281,19 +1281,27 @@ class Sequential(torch.nn.Module):
 
     def __init__(self, input_args, modules):
         super().__init__()
-        self.arg_names = [a.strip() for a in input_args.split(",")]
+
+        def names(text):    # ("x, adj, -> ..." is accepted as PyG accepts it: the empty name is ignored)
+            return [a.strip() for a in text.split(",") if a.strip()]
+
+        self.arg_names = names(input_args)
         self._plan = []
         for i, entry in enumerate(modules):
             if isinstance(entry, (tuple, list)):
                 mod, sig = entry
                 lhs, rhs = sig.split("->")
-                ins = [a.strip() for a in lhs.split(",")]
-                outs = [a.strip() for a in rhs.split(",")]
+                ins, outs = names(lhs), names(rhs)
             else:
                 mod = entry
                 prev = self._plan[-1][2] if self._plan else self.arg_names[:1]
                 ins, outs = list(prev), list(prev)
-            self.add_module(f"module_{i}", mod)
+            if isinstance(mod, torch.nn.Module):
+                self.add_module(f"module_{i}", mod)
+            elif callable(mod):     # a plain function (`lambda x: x`): a stage without parameters, same numbering
+                setattr(self, f"module_{i}", mod)
+            else:
+                raise TypeError(f"Sequential: stage {i} is neither a Module nor a callable: {mod!r}")
             self._plan.append((f"module_{i}", ins, outs))
 
     def stages(self):

@@ -467,6 +467,10 @@ int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_p
  * Declared in gcm_hip_mp.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_mp.h"
 
+/* ---- gcm.gcm.DenseToSparse / SparseToDense: adjacency <-> edge list with its index (csrc/dense_sparse.hip) ----
+ * Declared in gcm_hip_bridge.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_bridge.h"
+
 /* ---- LearnedEdge (src/gcm/edge_selectors/learned.py:53-125) ------------------- */
 
 /* learned.py:66-72: pairs[b, j, :] = cat(nodes[b, cur_b], nodes[b, j]) for j < cur_b, zero rows
