@@ -46,6 +46,8 @@ TAG_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_tag.h"))
 _PNA_HEADER = _abi.header("gcm_hip_pna.h")
 PNA_PROTOTYPES = _abi.prototypes(_PNA_HEADER)
 _CONSTANTS.update(_abi.constants(_PNA_HEADER))
+# and the section from gcm_hip_rgcn.h (RGCNConv / DenseRGCNConv, and the merge of the TypedEdge selector)
+RGCN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_rgcn.h"))
 # and the section from gcm_hip_gen.h (the softmax aggregation of GENConv / DenseGENConv and its gradients)
 GEN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gen.h"))
 # and the section from gcm_hip_edgeconv.h (the per-edge MLP and max of EdgeConv / DenseEdgeConv and its gradients)
@@ -119,6 +121,7 @@ def lib():
         bind(handle, GATED_PROTOTYPES)
         bind(handle, TAG_PROTOTYPES)
         bind(handle, PNA_PROTOTYPES)
+        bind(handle, RGCN_PROTOTYPES)
         bind(handle, GEN_PROTOTYPES)
         bind(handle, EDGECONV_PROTOTYPES)
         bind(handle, MP_PROTOTYPES)

@@ -1832,6 +1832,149 @@ def csr_pnaconv(x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, graph, c
 
 
 # ---------------------------------------------------------------------------
+# RGCNConv / DenseRGCNConv and TypedEdge's merge (csrc/rgcnconv.hip)
+# ---------------------------------------------------------------------------
+RGCN_MAX_RELATIONS = 16
+RGCN_MAX_WIDTH = 128
+
+
+def _rgcn_limits(Fi, Fo, R):
+    if Fi > RGCN_MAX_WIDTH or Fo > RGCN_MAX_WIDTH or R > RGCN_MAX_RELATIONS:
+        raise NotImplementedError(f"RGCNConv kernels cover in/out channels <= {RGCN_MAX_WIDTH} and <= "
+                                  f"{RGCN_MAX_RELATIONS} relations; got {Fi} -> {Fo}, {R} relations")
+
+
+def _rgcn_call(name, *args):
+    rc = getattr(_hip.lib(), name)(*args)
+    if rc == _hip.GCM_EUNSUPPORTED:
+        raise NotImplementedError(f"{name}: shape outside what the kernels are built for")
+    _hip.check(rc, name)
+
+
+class _DenseRGCNConv(torch.autograd.Function):
+    """x [B,N,Fi], adj / rel [B,N,N] float32, weight [R,Fi,Fo], root [Fi,Fo] or None, bias [Fo] or None."""
+
+    @staticmethod
+    def forward(ctx, x, adj, rel, weight, root, bias, mean):
+        x, adj, rel, weight = x.contiguous(), adj.contiguous(), rel.contiguous(), weight.contiguous()
+        root, bias = _contig(root), _contig(bias)
+        _hip.on_device(x, adj, rel, weight, root, bias)
+        B, N, Fi = x.shape
+        R, _, Fo = weight.shape
+        assert adj.shape == (B, N, N), "adj must be [B, N, N]"
+        assert rel.shape == (B, N, N) and rel.dtype == _f32, "rel must be a float32 [B, N, N]"
+        assert weight.shape == (R, Fi, Fo) and (root is None or root.shape == (Fi, Fo))
+        _rgcn_limits(Fi, Fo, R)
+        dev = x.device
+        out = torch.empty(B, N, Fo, device=dev, dtype=_f32)
+        scale = torch.empty(B, R, N, device=dev, dtype=_f32) if mean else None
+        ws, ws_bytes = _scratch("gcm_dense_rgcnconv_fwd", B, N, Fi, Fo, R, device=dev)
+        _rgcn_call("gcm_dense_rgcnconv_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(rel), _hip.ptr(weight),
+                   _hip.ptr(root), _hip.ptr(bias), _hip.ptr(out), _hip.ptr(scale), _hip.ptr(ws), ws_bytes, B, N, Fi,
+                   Fo, R, int(mean), _hip.stream())
+        ctx.save_for_backward(x, adj, rel, weight, root, scale)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, adj, rel, weight, root, scale = ctx.saved_tensors
+        B, N, Fi = x.shape
+        R, _, Fo = weight.shape
+        need_x, need_adj, _, need_w, need_root, need_b, _ = ctx.needs_input_grad
+        need_root = need_root and root is not None
+        need_b = need_b and ctx.has_bias
+        g_out = g_out.contiguous()
+        dev = x.device
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_w = torch.empty_like(weight) if need_w else None
+        g_root = torch.empty_like(root) if need_root else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws, ws_bytes = _scratch("gcm_dense_rgcnconv_bwd", B, N, Fi, Fo, R, device=dev)
+        _rgcn_call("gcm_dense_rgcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(rel),
+                   _hip.ptr(weight), _hip.ptr(root), _hip.ptr(scale), _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_w),
+                   _hip.ptr(g_root), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, B, N, Fi, Fo, R, _hip.stream())
+        return g_x, g_adj, None, g_w, g_root, g_b, None
+
+
+def dense_rgcnconv(x, adj, rel, weight, root, bias, mean):
+    return _DenseRGCNConv.apply(x, adj, rel, weight, root, bias, mean)
+
+
+class _CsrRGCNConv(torch.autograd.Function):
+    """x [M,Fi]; edge_type [E] int64 in CSR order: relation ids, or bit codes when mask_mode."""
+
+    @staticmethod
+    def forward(ctx, x, edge_type, weight, root, bias, graph, mean, mask_mode):
+        x, weight = x.contiguous(), weight.contiguous()
+        root, bias, edge_type = _contig(root), _contig(bias), edge_type.contiguous()
+        _hip.on_device(x, edge_type, weight, root, bias)
+        M, Fi = x.shape
+        R, _, Fo = weight.shape
+        E = graph.E
+        assert M == graph.M and edge_type.numel() == E and edge_type.dtype == _i64
+        assert weight.shape == (R, Fi, Fo) and (root is None or root.shape == (Fi, Fo))
+        _rgcn_limits(Fi, Fo, R)
+        dev = x.device
+        out = torch.empty(M, Fo, device=dev, dtype=_f32)
+        scale = torch.empty(M, R, device=dev, dtype=_f32) if mean else None
+        ws, ws_bytes = _scratch("gcm_csr_rgcnconv_fwd", M, E, Fi, Fo, R, device=dev)
+        _rgcn_call("gcm_csr_rgcnconv_fwd", _hip.ptr(x), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+                   _hip.ptr(edge_type), _hip.ptr(weight), _hip.ptr(root), _hip.ptr(bias), _hip.ptr(out),
+                   _hip.ptr(scale), _hip.ptr(ws), ws_bytes, M, E, Fi, Fo, R, int(mean), int(mask_mode), _hip.stream())
+        ctx.save_for_backward(x, edge_type, weight, root, scale)
+        ctx.graph, ctx.has_bias, ctx.mask_mode = graph, bias is not None, int(mask_mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, edge_type, weight, root, scale = ctx.saved_tensors
+        graph = ctx.graph
+        M, Fi = x.shape
+        R, _, Fo = weight.shape
+        E = graph.E
+        need_x, _, need_w, need_root, need_b, _, _, _ = ctx.needs_input_grad
+        need_root = need_root and root is not None
+        need_b = need_b and ctx.has_bias
+        g_out = g_out.contiguous()
+        dev = x.device
+        col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_w) and E > 0)
+        g_x = torch.empty_like(x) if need_x else None
+        g_w = torch.empty_like(weight) if need_w else None
+        g_root = torch.empty_like(root) if need_root else None
+        g_b = torch.empty(Fo, device=dev, dtype=_f32) if need_b else None
+        ws, ws_bytes = _scratch("gcm_csr_rgcnconv_bwd", M, E, Fi, Fo, R, device=dev)
+        _rgcn_call("gcm_csr_rgcnconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(edge_type), _hip.ptr(col_ptr),
+                   _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(weight), _hip.ptr(root), _hip.ptr(scale), _hip.ptr(g_x),
+                   _hip.ptr(g_w), _hip.ptr(g_root), _hip.ptr(g_b), _hip.ptr(ws), ws_bytes, M, E, Fi, Fo, R,
+                   ctx.mask_mode, _hip.stream())
+        return g_x, None, g_w, g_root, g_b, None, None, None
+
+
+def csr_rgcnconv(x, edge_type, weight, root, bias, graph, mean, mask_mode):
+    return _CsrRGCNConv.apply(x, edge_type, weight, root, bias, graph, mean, mask_mode)
+
+
+def typed_merge(adj, rel, children, bits, with_adj):
+    """rel | the bits of the children's selections, and with_adj the diff_or of adj and the children: one launch.
+    -> (adj_out or None, rel_out); nothing here carries a gradient."""
+    adj, rel = adj.contiguous(), rel.contiguous()
+    children = [c.detach().contiguous() for c in children]
+    _hip.on_device(adj, rel, *children)
+    assert rel.dtype == _f32 and all(c.shape == rel.shape and c.dtype == _f32 for c in children)
+    K = len(children)
+    adj_out = torch.empty_like(adj) if with_adj else None
+    rel_out = torch.empty_like(rel)
+    ptrs = (ctypes.c_void_p * K)(*[c.data_ptr() for c in children])
+    codes = (ctypes.c_int * K)(*bits)
+    _rgcn_call("gcm_typed_merge", _hip.ptr(adj), _hip.ptr(rel), ctypes.cast(ptrs, ctypes.c_void_p),
+               ctypes.cast(codes, ctypes.c_void_p), K, _hip.ptr(adj_out), _hip.ptr(rel_out), rel.numel(),
+               _hip.stream())
+    return adj_out, rel_out
+
+
+# ---------------------------------------------------------------------------
 # GENConv / DenseGENConv (PyG, aggr="softmax"; csrc/genconv.hip): the softmax aggregation alone - lin_src / lin_dst,
 # the message norm and the mlp stay in torch
 # ---------------------------------------------------------------------------

@@ -7,4 +7,7 @@ knn.KNNEdge                                           k nearest stored nodes (L2
                                                       distances, ranks and the adjacency row in one kernel
 learned.LearnedEdge                                   candidate pairs + gumbel-softmax/STE kernels
                                                       around a user-replaceable edge network
+typed.TypedEdge                                       several of the above side by side; which child selected an
+                                                      entry goes into the `weights` plane as a bit code
+                                                      (DenseGCM(edge_weights=True), gcm.nn.DenseRGCNConv)
 """

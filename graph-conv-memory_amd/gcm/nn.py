@@ -1016,6 +1016,158 @@ class PNAConv(torch.nn.Module):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, towers={self.towers})"
 
 
+_RGCN_AGGRS = ("mean", "add", "sum")
+
+
+def _rgcn_params(conv, name, in_channels, out_channels, num_relations, num_bases, num_blocks, aggr, root_weight, bias):
+    """PyG 2.x's parameters: weight [R or num_bases, Fin, Fout], comp [R, num_bases] with bases, root [Fin, Fout],
+    bias [Fout]."""
+    if num_blocks is not None:
+        raise NotImplementedError(f"{name}(num_blocks=...) is not implemented: the block-diagonal decomposition has "
+                                  "no kernel; use num_bases or full weights")
+    if not isinstance(in_channels, int) or isinstance(in_channels, bool):
+        raise NotImplementedError(f"{name}: in_channels must be an int (a tuple is a bipartite graph and None an "
+                                  "embedding lookup; neither is implemented)")
+    if aggr not in _RGCN_AGGRS:
+        raise NotImplementedError(f"{name}: aggr='{aggr}' is not implemented: one of {_RGCN_AGGRS}")
+    if num_relations > _ops.RGCN_MAX_RELATIONS:
+        raise NotImplementedError(f"{name}: num_relations={num_relations} is not implemented: the relation codes "
+                                  f"carry {_ops.RGCN_MAX_RELATIONS} bits")
+    if num_relations < 1 or (num_bases is not None and num_bases < 1):
+        raise ValueError(f"{name}: num_relations and num_bases must be >= 1")
+    conv.in_channels, conv.out_channels, conv.num_relations = in_channels, out_channels, num_relations
+    conv.num_bases, conv.num_blocks, conv.aggr = num_bases, num_blocks, aggr
+    if num_bases is not None:
+        conv.weight = torch.nn.Parameter(torch.empty(num_bases, in_channels, out_channels))
+        conv.comp = torch.nn.Parameter(torch.empty(num_relations, num_bases))
+    else:
+        conv.weight = torch.nn.Parameter(torch.empty(num_relations, in_channels, out_channels))
+        conv.register_parameter("comp", None)
+    if root_weight:
+        conv.root = torch.nn.Parameter(torch.empty(in_channels, out_channels))
+    else:
+        conv.register_parameter("root", None)
+    if bias:
+        conv.bias = torch.nn.Parameter(torch.empty(out_channels))
+    else:
+        conv.register_parameter("bias", None)
+    conv.reset_parameters()
+
+
+def _rgcn_reset(conv):
+    """PyG's glorot (uniform within sqrt(6 / (size(-2) + size(-1)))) for weight, comp and root; zeros for bias."""
+    for p in (conv.weight, conv.comp, conv.root):
+        if p is not None:
+            bound = (6.0 / (p.shape[-2] + p.shape[-1])) ** 0.5
+            torch.nn.init.uniform_(p, -bound, bound)
+    if conv.bias is not None:
+        torch.nn.init.zeros_(conv.bias)
+
+
+def _rgcn_weight(conv):
+    """[R, Fin, Fout]: the weights, or with bases comp . weight composed in torch under autograd."""
+    if conv.comp is None:
+        return conv.weight
+    return (conv.comp @ conv.weight.view(conv.num_bases, -1)).view(conv.num_relations, conv.in_channels,
+                                                                   conv.out_channels)
+
+
+def _rgcn_codes(t, what):
+    """Relation bit codes as the kernels read them; int64 codes keep their low 16 bits (more than any layer has)."""
+    if t.dtype == torch.int64:
+        return t.clamp(min=0) & 0xFFFF
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (holding integers) or int64; got {t.dtype}")
+    return t
+
+
+def _rgcn_repr(conv):
+    return f"{conv.__class__.__name__}({conv.in_channels}, {conv.out_channels}, num_relations={conv.num_relations})"
+
+
+_RGCN_DOC = """out_i = sum_r s_r(i) sum_j m_r(i,j) a(i,j) x_j W_r + x_i root + bias (Schlichtkrull et al., Modeling
+    Relational Data with Graph Convolutional Networks): one weight matrix per relation.  s_r(i) = 1 / max(1, number of
+    neighbours of i in relation r) for aggr="mean" - a count of the pattern, not of the values - and 1 for "add" /
+    "sum"; a node without neighbours in a relation gets nothing from it.  Parameters as PyG 2.x: weight [R, Fin, Fout]
+    (with num_bases: weight [num_bases, Fin, Fout] and comp [R, num_bases], composed in torch), root [Fin, Fout], bias
+    [Fout]; glorot / zeros; the dense and the sparse layer load each other's state_dict.  Forward and backward are HIP
+    kernels (csrc/rgcnconv.hip), float32, Fin, Fout <= 128, num_relations <= 16, bitwise reproducible.  num_blocks, a
+    tuple or None for in_channels and other aggregations raise NotImplementedError."""
+
+
+class DenseRGCNConv(torch.nn.Module):
+    __doc__ = """The relational GCN on a dense adjacency with a RELATION PLANE: x [B,N,Fin], adj [B,N,N] float
+    (adj[b,i,j]: i aggregates from j; its values are weights a(i,j) and get a gradient - a LearnedEdge stays trainable
+    through this layer), rel of adj's shape, float32 holding integers or int64: bit r of rel[b,i,j] set means the entry
+    lies in relation r; an entry may lie in several; codes <= 0 are no edge and bits >= num_relations are ignored.
+    rel never gets a gradient.  In a DenseGCM(edge_weights=True) the plane is the memory's `weights`, written by
+    edge_selectors.typed.TypedEdge: (DenseRGCNConv(F, H, sel.num_relations), "x, adj, weights -> x").  2-D input, a
+    broadcast [1,N,N] adjacency and `mask` as in the other dense layers.
+    """ + _RGCN_DOC + """  Not a DenseGraphConv: DenseGCM runs a stack of these through its layered path."""
+
+    def __init__(self, in_channels, out_channels, num_relations, num_bases=None, num_blocks=None, aggr="mean",
+                 root_weight=True, bias=True):
+        super().__init__()
+        _rgcn_params(self, "DenseRGCNConv", in_channels, out_channels, num_relations, num_bases, num_blocks, aggr,
+                     root_weight, bias)
+
+    def reset_parameters(self):
+        _rgcn_reset(self)
+
+    def forward(self, x, adj, rel, mask=None):
+        x, adj = _dense_inputs(x, adj)
+        rel = _rgcn_codes(rel, "rel")
+        rel = rel.unsqueeze(0) if rel.dim() == 2 else rel
+        if rel.shape[0] != x.shape[0]:
+            rel = rel.expand(x.shape[0], -1, -1)
+        _hip.on_device(x, self.weight)     # a CPU call fails here
+        out = _ops.dense_rgcnconv(x, adj, rel.detach().to(torch.float32), _rgcn_weight(self), self.root, self.bias,
+                                  self.aggr == "mean")
+        return _masked(out, mask, x)
+
+    def __repr__(self):
+        return _rgcn_repr(self)
+
+
+class RGCNConv(torch.nn.Module):
+    __doc__ = """PyG's RGCNConv (flow source_to_target): x [M,Fin], edge_index [2,E] = (source, sink), edge_type [E]
+    int64 relation ids.  An id outside [0, num_relations) contributes nothing; duplicate edges and self loops are
+    separate messages, no loop is added; every edge has the value 1.  is_sorted is accepted and ignored.
+    relation_mask=True (an extension): edge_type holds bit codes instead (int64, or float32 holding integers), so an
+    edge may lie in several relations - the values of DenseToSparse(transpose=True, edge_values=True)(x, rel) go
+    straight in.  Uses the `edge_index.gcm_graph` index when one is attached; any other edge list is indexed here.
+    """ + _RGCN_DOC + """  Not a GraphConv: SparseGCM runs a stack of these through its generic path."""
+
+    def __init__(self, in_channels, out_channels, num_relations, num_bases=None, num_blocks=None, aggr="mean",
+                 root_weight=True, is_sorted=False, bias=True, relation_mask=False):
+        super().__init__()
+        self.is_sorted, self.relation_mask = is_sorted, bool(relation_mask)
+        _rgcn_params(self, "RGCNConv", in_channels, out_channels, num_relations, num_bases, num_blocks, aggr,
+                     root_weight, bias)
+
+    def reset_parameters(self):
+        _rgcn_reset(self)
+
+    def forward(self, x, edge_index, edge_type):
+        _hip.on_device(x, self.weight)     # a CPU call fails here, before the index is built
+        graph = _graph_of(x, edge_index, "RGCNConv")
+        if edge_type is None or edge_type.numel() != graph.E:
+            raise ValueError(f"RGCNConv: edge_type must hold one entry per edge ({graph.E})")
+        if self.relation_mask:
+            et = _rgcn_codes(edge_type.detach(), "edge_type").to(torch.int64)
+        elif edge_type.dtype != torch.int64:
+            raise TypeError(f"RGCNConv: edge_type must be int64 relation ids; got {edge_type.dtype}")
+        else:
+            et = edge_type
+        if graph.csr_perm is not None:
+            et = et[graph.csr_perm]
+        return _ops.csr_rgcnconv(x, et, _rgcn_weight(self), self.root, self.bias, graph, self.aggr == "mean",
+                                 self.relation_mask)
+
+    def __repr__(self):
+        return _rgcn_repr(self)
+
+
 class _SoftmaxAggr(torch.nn.Module):
     """Holder of GENConv's temperature under PyG's key `aggr_module.t` [1]: a Parameter when learnt, else a
     persistent buffer."""

@@ -455,6 +455,10 @@ int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_p
  * Declared in gcm_hip_pna.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_pna.h"
 
+/* ---- RGCNConv / DenseRGCNConv and the TypedEdge selector's merge (PyG; csrc/rgcnconv.hip) ----
+ * Declared in gcm_hip_rgcn.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_rgcn.h"
+
 /* ---- GENConv / DenseGENConv softmax aggregation (PyG; csrc/genconv.hip) ----
  * Declared in gcm_hip_gen.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_gen.h"
