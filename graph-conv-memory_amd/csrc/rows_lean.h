@@ -20,6 +20,22 @@ __device__ __forceinline__ float lean_half_matvec(const f32x2 (&w)[16], const fl
   return gcm_xor32_add(acc[0] + acc[1]);
 }
 
+// The same chain for a lane that makes BOTH K halves of its column itself (the multi-step kernel: a step per half-wave)
+// and adds them in lean_half_matvec's order, half 0's sum + half 1's: lean_half_chain(.., 0) + lean_half_chain(.., 1).
+// It repeats the loop above word for word - keep the two alike - instead of sharing a helper with it: with a shared
+// helper the compiler swaps the operands of two packed adds in the lean kernel, whose code is to stay what it is.
+__device__ __forceinline__ float lean_half_chain(const f32x2 (&w)[16], const float* sv, int kh) {
+  f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const f32x4 u = *reinterpret_cast<const f32x4*>(sv + 32 * kh + 4 * j);
+    acc0 = w[2 * j] * f32x2{u[0], u[1]} + acc0;
+    acc1 = w[2 * j + 1] * f32x2{u[2], u[3]} + acc1;
+  }
+  const f32x2 acc = acc0 + acc1;
+  return acc[0] + acc[1];
+}
+
 // Is this cached step the lean case - and if so, which step?  The ONE decision both gcm_dense_rows_step_cached_ws and
 // the run entry (rows_cached_run.hip) take: a weight image in its interleaved form, no distance selector, neither
 // GCM_STEP_ONE_WAVE nor GCM_STEP_NOT_LEAN, F = H1 = 32, 0 < H2 <= 32, tanh / tanh, the row known on the host
