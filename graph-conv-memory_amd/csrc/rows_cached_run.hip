@@ -30,12 +30,18 @@
 //   * what follows from cur and the hops alone (adjacency entries, the record's live list / coefficients / header) is
 //     written at the end in closed form, eight lanes per step and eight steps per wave instruction, the count once
 //     with the run's last value.
+//
+// The same reasoning removes the rollout's head launch (k_head_fused, head_fused.hip) when it sits directly in front of
+// step 0: the node that replaces the lean node at the first append is added on the head's dependencies and runs the
+// kernel's FRESH form, which does the head's work itself ("the head absorbed" below; gcm_hip_run_head.h).
 #include <atomic>
 #include <new>
+#include <type_traits>
 
 #include "fused_common.h"
 #include "gcm_common.h"
 #include "rows_common.h"
+#include "rows_head.h"
 #include "rows_lean.h"
 
 namespace gcm_rows {
@@ -51,18 +57,53 @@ struct RunTable {
   float* rec[RUN_CAP];
 };
 
+// What the fresh-state form (FRESH) does in place of the rollout's head launch (k_head_fused, absorbed at capture time:
+// "the head absorbed" below): the head's sources, the packed vector and the image it wrote, and the 64-float paddings of
+// the state allocation nodes | adj | count it zeroed (floats from `nodes`: [pad0, pad0_end) and [pad1, pad1_end)).
+struct FreshArgs {
+  HeadSrcs hs;
+  float* packed;
+  float* image;
+  unsigned pad0, pad0_end, pad1, pad1_end;
+};
+struct NoFresh {};
+constexpr int RUN_ADJ_TAB = 256 + 128;   // FRESH: the adjacency pattern by column - row + 128, then a row of zeros
+
+// Where the FRESH form's state / image / packed stores sit: 0 behind the first barrier (the pattern table is made in
+// phase A), 1 at the end with phase D.  Measured on cfg2 (profiles/r12_bench_cfg2_cuts.jsonl): 0.0604 - 0.0614 ms per
+// rollout against 0.0614 - 0.0634 - issued early they drain under phases B and C.
+#ifndef GCM_RUN_FRESH_STORES_LATE
+#define GCM_RUN_FRESH_STORES_LATE 0
+#endif
+
 // hops4: the distinct hops 0 < h < 128 ASCENDING, one byte each, 0xff in the unused slots.  nhs: N | H2 << 8 | self << 16.
 // Steps t < n <= RUN_CAP: row cur0 + t < N, observation tab.obs[t] [B, 32], record tab.rec[t] (o_*: CachedLayout;
 // rec = 0: mx alone).
+//
+// FRESH: the run starts at row 0 of the empty graphs the rollout's head launch would have made, and that launch is not
+// in the graph: this kernel does its work ("the head absorbed").  N % 4 == 0, cur0 == 0.
+//   * the weights come from the parameter tensors themselves (fr.hs: W_rel1, W_root1, b1, W_rel2, W_root2, b2 lead it),
+//     sixteen bytes of a row per load, and reach the LDS image through the index map k_head_fused writes layout 3 with
+//     (rows_head.h); `image` and `params` are not read;
+//   * the packed vector and the three image layouts are written to global memory for the backward and later launches:
+//     workgroup g makes elements g, g + B, ... with k_head_fused's own expressions (the first round's loads are issued
+//     with the other loads; further rounds, at B < 32, run at the end);
+//   * the graph's state is written whole: node rows [n, N) zero, adjacency rows [0, n) in closed form - one 16-byte
+//     store per four columns, 1.0 at the sources (and at cur with self) and 0.0 elsewhere, read from a pattern table in
+//     LDS indexed by column - row - and rows [n, N) zero; workgroup 0 zeroes the paddings of the allocation.  Every
+//     address is stored once, so no order between waves is needed; phase D's scalar adjacency stores are left out.
+template <bool FRESH>
 __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_run(
     const float* __restrict__ image, float* __restrict__ nodes, float* __restrict__ cH, const float* __restrict__ params,
-    int cur0, int n, unsigned hops4, unsigned nhs, float* __restrict__ adj, int64_t* __restrict__ count,
+    int cur0_arg, int n, unsigned hops4, unsigned nhs, float* __restrict__ adj, int64_t* __restrict__ count,
     float* __restrict__ cA, float* __restrict__ cX, uint32_t* __restrict__ flags, unsigned o_v, unsigned o_hdr,
-    unsigned o_coef, unsigned o_live, int rec, RunTable tab) {
+    unsigned o_coef, unsigned o_live, int rec, RunTable tab, std::conditional_t<FRESH, FreshArgs, NoFresh> fr) {
   constexpr int F = 32, H1 = 32, ROWS = 128 * 32;
+  const int cur0 = FRESH ? 0 : cur0_arg;
   __shared__ __attribute__((aligned(16))) float sXH[2 * ROWS];            // x rows [128][32] | h1 rows [128][32]
   __shared__ __attribute__((aligned(16))) float svw[RUN_WAVES * 128];     // each wave's lane exchange: two steps' vectors
   __shared__ __attribute__((aligned(16))) f32x2 sW[2 * 16 * 32 * 2];      // image3 as [layer][k][h][K half]: 16 KB
+  __shared__ float sadj[FRESH ? RUN_ADJ_TAB : 1];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const unsigned gb = blockIdx.x;
@@ -95,13 +136,38 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   }
   // the weight image goes through LDS, loaded once per workgroup: a lane needs both K halves of a layer (64 registers),
   // so layer 2's wait there until phase C
-  const f32x2* i3 = reinterpret_cast<const f32x2*>(image + 2 * 4 * 64 * 64);   // image3 (k_cached_weight_image)
   f32x2 wst[RUN_WSTAGE];
+  f32x4 wq[2];
+  float bias1, bias2;
+  // FRESH: this workgroup's first elements of the image and of the packed vector (element gb + B * thread)
+  float v_img = 0.f, v_pack = 0.f;
+  const size_t e_first = (size_t)gb + (size_t)gridDim.x * threadIdx.x, e_wave = (size_t)gb + (size_t)gridDim.x * (64 * wv);
+  if constexpr (!FRESH) {
+    const f32x2* i3 = reinterpret_cast<const f32x2*>(image + 2 * 4 * 64 * 64);   // image3 (k_cached_weight_image)
 #pragma unroll
-  for (int r = 0; r < RUN_WSTAGE; ++r) wst[r] = i3[(int)threadIdx.x + 64 * RUN_WAVES * r];
-  const float* b1 = params + 2 * H1 * F;
-  const float bias1 = b1[fl];
-  const float bias2 = b1[H1 + 2 * H2 * H1 + ol];
+    for (int r = 0; r < RUN_WSTAGE; ++r) wst[r] = i3[(int)threadIdx.x + 64 * RUN_WAVES * r];
+    const float* b1 = params + 2 * H1 * F;
+    bias1 = b1[fl];
+    bias2 = b1[H1 + 2 * H2 * H1 + ol];
+  } else {
+    // quad q = thread + 512 r of [m][h][k / 4]: columns 4 (q & 7) ... + 3 of row h of matrix m (zero past row H2)
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int q = (int)threadIdx.x + 64 * RUN_WAVES * r;
+      const int m = q >> 8, h = (q >> 3) & 31;
+      const float* w = m == 0 ? fr.hs.p[0] : m == 1 ? fr.hs.p[1] : m == 2 ? fr.hs.p[3] : fr.hs.p[4];
+      wq[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (m < 2 || h < H2) wq[r] = *reinterpret_cast<const f32x4*>(w + h * 32 + 4 * (q & 7));
+    }
+    bias1 = fr.hs.p[2][fl];
+    bias2 = fr.hs.p[5][ol];
+    if (e_wave < (size_t)IMG_LAYOUT_FLOATS && e_first < (size_t)IMG_LAYOUT_FLOATS) {
+      const int e = (int)e_first;
+      v_img = head_image_value(fr.hs, e >> 12, (e >> 6) & 63, e & 63, F, H1, H2);
+    }
+    if (e_wave < fr.hs.off[HEAD_MAX_SRCS] && e_first < fr.hs.off[HEAD_MAX_SRCS])
+      v_pack = head_packed_value(fr.hs, (unsigned)e_first);
+  }
   // the rows from before the run that a step of it can read: [cur0 - max(hop), cur0), x (lanes 0 - 31) and h1 (32 - 63)
   int hmax = 0, nh = 0;
 #pragma unroll
@@ -117,10 +183,29 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
     const float* src = hs ? cH : nodes;
     for (int r = lo + wv; r < cur0; r += RUN_WAVES) sXH[hs * ROWS + r * 32 + fl] = src[(g0 + (unsigned)r) * 32 + fl];
   }
+  if constexpr (!FRESH) {
 #pragma unroll
-  for (int r = 0; r < RUN_WSTAGE; ++r) {   // image3 element (layer, k, lane l): [layer][k][l & 31][l >> 5]
-    const int e = (int)threadIdx.x + 64 * RUN_WAVES * r;
-    sW[((e >> 6) * 32 + (e & 31)) * 2 + ((e >> 5) & 1)] = wst[r];
+    for (int r = 0; r < RUN_WSTAGE; ++r) {   // image3 element (layer, k, lane l): [layer][k][l & 31][l >> 5]
+      const int e = (int)threadIdx.x + 64 * RUN_WAVES * r;
+      sW[image3_lds_pair(e)] = wst[r];
+    }
+  } else {
+    float* sWf = reinterpret_cast<float*>(sW);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int q = (int)threadIdx.x + 64 * RUN_WAVES * r;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sWf[image3_lds_index(q >> 8, 4 * (q & 7) + u, (q >> 3) & 31)] = wq[r][u];
+    }
+    // the adjacency pattern: entry x is column - row + 128, 1.0 where row - column is a hop (or 0 with self); from 256
+    // on a row of zeros (the rows past the run's end)
+    if (threadIdx.x < RUN_ADJ_TAB) {
+      const int d = 128 - (int)threadIdx.x;
+      bool hit = d == 0 && self;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) hit = hit || (d > 0 && (int)((hops4 >> (8 * i)) & 0xffu) == d);
+      sadj[threadIdx.x] = hit && threadIdx.x < 256 ? 1.f : 0.f;
+    }
   }
 #pragma unroll
   for (int j = 0; j < RUN_PAIRS; ++j) {   // the observations: x rows in LDS, rows of the node matrix and of its cache
@@ -133,6 +218,29 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
     }
   }
   __syncthreads();
+  // FRESH: what the head launch wrote, and the rest of this graph's state (no load follows: loads and stores share vmcnt)
+  auto fresh_stores = [&]() {
+    if constexpr (FRESH) {
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      const int nq = (int)(N >> 2);   // 16-byte stores per adjacency row: a half-wave makes a row
+      f32x4* arow = reinterpret_cast<f32x4*>(adj + (size_t)g0 * N);
+      for (int r = 2 * wv + hs; r < (int)N; r += 2 * RUN_WAVES) {
+        if (fl < nq) {
+          const float* at = sadj + (r < n ? 128 + 4 * fl - r : 256);
+          arow[r * nq + fl] = f32x4{at[0], at[1], at[2], at[3]};
+        }
+      }
+      f32x4* nrow = reinterpret_cast<f32x4*>(nodes + (size_t)g0 * F);
+      for (int i = n * (F / 4) + (int)threadIdx.x; i < (int)N * (F / 4); i += 64 * RUN_WAVES) nrow[i] = z;
+      if (gb == 0 && threadIdx.x < 64) {
+        if (fr.pad0 + threadIdx.x < fr.pad0_end) nodes[fr.pad0 + threadIdx.x] = 0.f;
+        if (fr.pad1 + threadIdx.x < fr.pad1_end) nodes[fr.pad1 + threadIdx.x] = 0.f;
+      }
+      if (e_wave < (size_t)IMG_LAYOUT_FLOATS && e_first < (size_t)IMG_LAYOUT_FLOATS) head_image_store(fr.image, (int)e_first, v_img);
+      if (e_wave < fr.hs.off[HEAD_MAX_SRCS] && e_first < fr.hs.off[HEAD_MAX_SRCS]) fr.packed[e_first] = v_pack;
+    }
+  };
+  if (!GCM_RUN_FRESH_STORES_LATE) fresh_stores();
   // the source rows of row cur, ascending and compacted as the lean kernel's host resolves them: the k hops <= cur are
   // the first k of the ascending list, slot q holds row cur - hop[k - 1 - q]; an empty slot reads row 0 and adds nothing
   auto sources = [&](int cur, const float* rows, float (&va)[4]) {
@@ -258,7 +366,7 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
       for (int i = 0; i < 4; ++i) k += (int)(((hops4 >> (8 * i)) & 0xffu) <= (unsigned)cur);
       const int j = q < k ? cur - (int)((hops4 >> (8 * ((k - 1 - q) & 3))) & 0xffu) : cur;
       const bool is_cur = q == k;
-      if (q < k || (is_cur && self)) adj[(size_t)(g0 + (unsigned)cur) * N + j] = 1.f;
+      if (!FRESH && (q < k || (is_cur && self))) adj[(size_t)(g0 + (unsigned)cur) * N + j] = 1.f;
       if (rec) {
         float* saved = recd[o];
         if (q <= k) {
@@ -275,6 +383,14 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   if (threadIdx.x == 0) count[gb] = cur0 + n;   // (nothing can observe the values in between)
   const bool nonfinite = __any(bad);
   if (nonfinite && lane == 0) atomicOr(flags, GCM_FLAG_NONFINITE);
+  if constexpr (FRESH) {
+    if (GCM_RUN_FRESH_STORES_LATE) fresh_stores();
+    // the further rounds of the image and the packed vector (a batch of fewer than 32 graphs)
+    const size_t step = (size_t)gridDim.x * (64 * RUN_WAVES);
+    for (size_t e = e_first + step; e < (size_t)IMG_LAYOUT_FLOATS; e += step)
+      head_image_store(fr.image, (int)e, head_image_value(fr.hs, (int)e >> 12, ((int)e >> 6) & 63, (int)e & 63, F, H1, H2));
+    for (size_t e = e_first + step; e < fr.hs.off[HEAD_MAX_SRCS]; e += step) fr.packed[e] = head_packed_value(fr.hs, (unsigned)e);
+  }
 }
 
 // ---- the host side: one run object per chain --------------------------------------------------------------------
@@ -295,7 +411,21 @@ struct Run {
   int cap = RUN_CAP;
   // counters of the capture seen last
   unsigned long long stat_cid = 0;
-  int stat_nodes = 0, stat_merged = 0;
+  int stat_nodes = 0, stat_merged = 0, stat_absorbed = 0;
+  // the head launch seen last under a capture (gcm_dense_rows_head_fused_run): looked at only while the stream's capture
+  // is head.cid.  fresh: the remembered node has absorbed it and runs the fresh-state form with `fr`
+  struct Head {
+    hipGraphNode_t node = nullptr;
+    unsigned long long cid = 0;
+    hipStream_t stream = nullptr;
+    HeadSrcs hs{};
+    float *packed = nullptr, *image = nullptr;
+    void* zero = nullptr;
+    size_t zero_bytes = 0;
+    int H2 = 0;
+  } head;
+  bool absorb = true, fresh = false;
+  FreshArgs fr{};
 };
 
 // a graph call failed once: every later step of the process is a launch of its own
@@ -307,12 +437,20 @@ static void merge_off(hipError_t e) {
   g_merge_ok = false;
   (void)hipGetLastError();
 }
+// a graph call of the head's absorption was refused once: heads stay launches of their own (merging itself goes on)
+static std::atomic<bool> g_absorb_ok{true};
+static void absorb_off(hipError_t e) {
+  g_last_error = (int)e;
+  g_absorb_ok = false;
+  (void)hipGetLastError();
+}
 
 // n steps of R (tab filled up to n) as the parameters of a kernel node
 struct RunArgs {
   int cur0, n, rec;
   unsigned hops4, nhs, o_v, o_hdr, o_coef, o_live;
-  void* ptr[19];
+  NoFresh none;
+  void* ptr[20];
   hipKernelNodeParams p;
 };
 static void fill_args(Run& R, int n, RunArgs& a) {
@@ -323,11 +461,12 @@ static void fill_args(Run& R, int n, RunArgs& a) {
   a.hops4 = R.hops4;
   a.nhs = (unsigned)R.N | (unsigned)R.H2 << 8 | (R.self ? 1u << 16 : 0u);
   a.o_v = (unsigned)lay.o_v; a.o_hdr = (unsigned)lay.o_hdr; a.o_coef = (unsigned)lay.o_coef; a.o_live = (unsigned)lay.o_live;
-  void* ptr[19] = {&R.image, &R.nodes, &R.cH, &R.params, &a.cur0, &a.n, &a.hops4, &a.nhs, &R.adj, &R.count,
-                   &R.cA,    &R.cX,    &R.flags, &a.o_v, &a.o_hdr, &a.o_coef, &a.o_live, &a.rec, &R.tab};
-  for (int i = 0; i < 19; ++i) a.ptr[i] = ptr[i];
+  void* ptr[20] = {&R.image, &R.nodes, &R.cH, &R.params, &a.cur0, &a.n, &a.hops4, &a.nhs, &R.adj, &R.count,
+                   &R.cA,    &R.cX,    &R.flags, &a.o_v, &a.o_hdr, &a.o_coef, &a.o_live, &a.rec, &R.tab,
+                   R.fresh ? (void*)&R.fr : (void*)&a.none};
+  for (int i = 0; i < 20; ++i) a.ptr[i] = ptr[i];
   a.p = hipKernelNodeParams{};
-  a.p.func = (void*)k_step_rows_cached_img4_lean_run;
+  a.p.func = R.fresh ? (void*)k_step_rows_cached_img4_lean_run<true> : (void*)k_step_rows_cached_img4_lean_run<false>;
   a.p.gridDim = dim3(R.B);
   a.p.blockDim = dim3(64 * RUN_WAVES);
   a.p.sharedMemBytes = 0;
@@ -342,7 +481,106 @@ static void fill_args(Run& R, int n, RunArgs& a) {
 // route is the one that runs there, and once it has, it is taken straight away.  The old node is replaced only while
 // nothing depends on it (a fork recorded behind step t on another stream would): else the step starts a new run.
 // false: nothing changed; the step is then a launch of its own (and after a failed graph call merging is off)
-static bool grow_node(Run& R, int n, hipGraph_t graph) {
+inline int64_t pad64(int64_t v) { return (v + 63) & ~int64_t(63); }
+
+// The head absorbed.  The first append of a run replaces the lean node by the multi-step node anyway; if
+// that lean node is step 0 of a rollout whose head launch (k_head_fused, remembered by gcm_dense_rows_head_fused_run)
+// sits directly in front of it - the lean node's only dependency is the head's node and the head's only dependent is
+// the lean node - no captured work can observe the head's outputs before the steps have run, and the new node does the
+// head's work itself (the kernel's FRESH form): it is added on the HEAD's dependencies, and both old nodes go.
+// -> 1: absorbed, R.node is the new node of n steps; 0: not absorbed and nothing changed (a refused graph call also
+// turns absorption off for the process); *broken set: the head's node could neither be destroyed nor ordered in front
+// of the new node - the graph must not be used, the entry returns the error.
+static int absorb_head(Run& R, int n, hipGraph_t graph, hipError_t* broken) {
+  const Run::Head& H = R.head;
+  if (!R.absorb || !g_absorb_ok.load() || R.fresh || R.cur0 != 0 || !H.node || H.cid != R.cid || H.stream != R.stream)
+    return 0;
+  const int64_t n_nodes = pad64((int64_t)R.B * R.N * 32), n_adj = pad64((int64_t)R.B * R.N * R.N);
+  const auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (H.packed != R.params || H.image != R.image || H.H2 != R.H2 || R.N % 4 != 0 || H.zero != (void*)R.nodes ||
+      H.zero_bytes != sizeof(float) * (size_t)(n_nodes + n_adj + 2 * (int64_t)R.B) || R.adj != R.nodes + n_nodes ||
+      reinterpret_cast<float*>(R.count) != R.nodes + n_nodes + n_adj || !aligned16(H.hs.p[0]) || !aligned16(H.hs.p[1]) ||
+      !aligned16(H.hs.p[3]) || !aligned16(H.hs.p[4]))
+    return 0;
+  size_t nd = 0, n_dep = 0, nh = 0;
+  hipGraphNode_t one = nullptr, hdeps[8];
+  hipError_t e = hipGraphNodeGetDependentNodes(R.node, nullptr, &n_dep);
+  if (e == hipSuccess && n_dep) return 0;
+  if (e == hipSuccess) e = hipGraphNodeGetDependencies(R.node, nullptr, &nd);
+  if (e == hipSuccess && nd != 1) return 0;
+  if (e == hipSuccess) e = hipGraphNodeGetDependencies(R.node, &one, &nd);
+  if (e == hipSuccess && (nd != 1 || one != H.node)) return 0;
+  if (e == hipSuccess) e = hipGraphNodeGetDependentNodes(H.node, nullptr, &n_dep);
+  if (e == hipSuccess && n_dep != 1) return 0;
+  if (e == hipSuccess) e = hipGraphNodeGetDependentNodes(H.node, &one, &n_dep);
+  if (e == hipSuccess && (n_dep != 1 || one != R.node)) return 0;
+  if (e == hipSuccess) e = hipGraphNodeGetDependencies(H.node, nullptr, &nh);
+  if (e == hipSuccess && nh > 8) return 0;
+  if (e == hipSuccess && nh) e = hipGraphNodeGetDependencies(H.node, hdeps, &nh);
+  if (e != hipSuccess) {
+    absorb_off(e);
+    return 0;
+  }
+  R.fr = FreshArgs{};
+  R.fr.hs = H.hs;
+  R.fr.packed = H.packed;
+  R.fr.image = H.image;
+  R.fr.pad0 = (unsigned)((int64_t)R.B * R.N * 32);
+  R.fr.pad0_end = (unsigned)n_nodes;
+  R.fr.pad1 = (unsigned)(n_nodes + (int64_t)R.B * R.N * R.N);
+  R.fr.pad1_end = (unsigned)(n_nodes + n_adj);
+  R.fresh = true;
+  RunArgs a;
+  fill_args(R, n, a);
+  hipGraphNode_t fresh = nullptr;
+  e = hipGraphAddKernelNode(&fresh, graph, nh ? hdeps : nullptr, nh, &a.p);
+  if (e != hipSuccess) {
+    R.fresh = false;
+    absorb_off(e);
+    return 0;
+  }
+  e = hipStreamUpdateCaptureDependencies(R.stream, &fresh, 1, hipStreamSetCaptureDependencies);
+  if (e == hipSuccess) {
+    e = hipGraphDestroyNode(R.node);
+    if (e != hipSuccess) {   // put the stream back on the lean node
+      hipGraphNode_t old = R.node;
+      (void)hipStreamUpdateCaptureDependencies(R.stream, &old, 1, hipStreamSetCaptureDependencies);
+    }
+  }
+  if (e != hipSuccess) {   // nothing is gone yet: the ordinary replacement follows
+    (void)hipGraphDestroyNode(fresh);
+    R.fresh = false;
+    absorb_off(e);
+    return 0;
+  }
+  R.node = fresh;
+  g_route = 2;
+  e = hipGraphDestroyNode(H.node);
+  if (e != hipSuccess) {
+    // The lean node is gone and the head is not.  Ordered in front of the new node the head is harmless - the fresh
+    // form rewrites every byte it wrote with the same values - but side by side they would race: order it, or give up.
+    absorb_off(e);
+    hipGraphNode_t from = H.node;
+    const hipError_t e2 = hipGraphAddDependencies(graph, &from, &fresh, 1);
+    if (e2 != hipSuccess) {
+      (void)hipGetLastError();
+      *broken = e;
+      R.node = nullptr;
+      R.head.node = nullptr;
+      return 0;
+    }
+  } else {
+    ++R.stat_absorbed;
+  }
+  R.head.node = nullptr;
+  return 1;
+}
+
+static bool grow_node(Run& R, int n, hipGraph_t graph, hipError_t* broken) {
+  if (R.n == 1 && n == 2) {
+    const int ab = absorb_head(R, n, graph, broken);
+    if (ab || *broken != hipSuccess) return ab == 1;
+  }
   RunArgs a;
   fill_args(R, n, a);
   if (g_route.load() != 2) {
@@ -421,6 +659,7 @@ extern "C" int gcm_rows_run_destroy(void* run) {
 extern "C" int gcm_rows_run_reset(void* run) {
   GCM_REQUIRE(run);
   static_cast<gcm_rows::Run*>(run)->node = nullptr;
+  static_cast<gcm_rows::Run*>(run)->fresh = false;
   return GCM_OK;
 }
 extern "C" int gcm_rows_run_set_cap(void* run, int cap) {
@@ -471,8 +710,10 @@ extern "C" int gcm_dense_rows_step_cached_run(void* run, const float* obs, float
   }
   if (cs != hipStreamCaptureStatusActive) {   // eager: exactly today's path
     R->node = nullptr;
+    R->head.node = nullptr;
+    R->fresh = false;
     R->stat_cid = 0;
-    R->stat_nodes = R->stat_merged = 0;
+    R->stat_nodes = R->stat_merged = R->stat_absorbed = 0;
     return plain();
   }
   // the lean case, as gcm_dense_rows_step_cached_ws decides it
@@ -485,6 +726,7 @@ extern "C" int gcm_dense_rows_step_cached_run(void* run, const float* obs, float
                     lean_step_case(selectors, n_selectors, weight_image, has_bias, act1, act2, N, F, H1, H2, cur_host, lc);
   if (!lean) {
     R->node = nullptr;
+    R->fresh = false;
     return plain();
   }
   const int self = lc.self;
@@ -498,7 +740,7 @@ extern "C" int gcm_dense_rows_step_cached_run(void* run, const float* obs, float
                             overlap(obs, obs_floats, adj, (size_t)B * N * N);
   if (R->stat_cid != cid) {
     R->stat_cid = cid;
-    R->stat_nodes = R->stat_merged = 0;
+    R->stat_nodes = R->stat_merged = R->stat_absorbed = 0;
   }
   // (a handle is looked at only while the stream's capture is the one it was made in)
   const bool follows = R->node && R->cid == cid && R->stream == st && nd == 1 && deps[0] == R->node &&
@@ -511,14 +753,17 @@ extern "C" int gcm_dense_rows_step_cached_run(void* run, const float* obs, float
   if (follows) {
     R->tab.obs[R->n] = obs;
     R->tab.rec[R->n] = saved;
-    if (grow_node(*R, R->n + 1, graph)) {
+    hipError_t broken = hipSuccess;
+    if (grow_node(*R, R->n + 1, graph, &broken)) {
       ++R->n;
       ++R->stat_merged;
       return GCM_OK;
     }
+    if (broken != hipSuccess) return (int)broken;   // (the graph is half-edited: the capture must fail)
   }
   // a new run: the lean kernel, captured as gcm_dense_rows_step_cached_ws captures it, and its node remembered
   R->node = nullptr;
+  R->fresh = false;
   if (!record) lay.total = 0;
   const int rc = launch_step_cached_lean(obs, nodes, adj, count, lc.m0, lc.m1, self, params, weight_image, cache_h1,
                                          cache_agg1, cache_nodes, saved, lay, flags, B, N, H2, cur_host, st);
@@ -554,4 +799,72 @@ extern "C" int gcm_dense_rows_step_cached_run(void* run, const float* obs, float
   R->tab.obs[0] = obs;
   R->tab.rec[0] = saved;
   return GCM_OK;
+}
+
+extern "C" int gcm_rows_run_set_absorb(void* run, int on) {
+  GCM_REQUIRE(run);
+  static_cast<gcm_rows::Run*>(run)->absorb = on != 0;
+  return GCM_OK;
+}
+extern "C" int gcm_rows_run_absorbed(const void* run) {
+  return run ? static_cast<const gcm_rows::Run*>(run)->stat_absorbed : 0;
+}
+extern "C" int gcm_rows_run_absorb_enabled(void) { return gcm_rows::g_absorb_ok.load() ? 1 : 0; }
+
+extern "C" int gcm_dense_rows_head_fused_run(void* run, const float* const* srcs_host, const size_t* lens_host, int n,
+                                             float* packed, float* image, int F, int H1, int H2, void* zero,
+                                             size_t zero_bytes, gcm_stream_t stream) {
+  using namespace gcm_rows;
+  const int rc = gcm_dense_rows_head_fused(srcs_host, lens_host, n, packed, image, F, H1, H2, zero, zero_bytes, stream);
+  Run* R = static_cast<Run*>(run);
+  if (!R) return rc;
+  R->head.node = nullptr;
+  if (rc != GCM_OK || !R->absorb || !g_absorb_ok.load() || !g_merge_ok.load() || !image || !zero || F != 32 || H1 != 32)
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  unsigned long long cid = 0;
+  hipGraph_t graph = nullptr;
+  const hipGraphNode_t* deps = nullptr;
+  size_t nd = 0;
+  hipError_t e = hipStreamGetCaptureInfo_v2(st, &cs, &cid, &graph, &deps, &nd);
+  if (e != hipSuccess) {
+    absorb_off(e);
+    return rc;
+  }
+  if (cs != hipStreamCaptureStatusActive || nd != 1) return rc;
+  hipGraphNode_t node = deps[0];
+  hipGraphNodeType type;
+  hipKernelNodeParams got;
+  if ((e = hipGraphNodeGetType(node, &type)) != hipSuccess ||
+      (type == hipGraphNodeTypeKernel && (e = hipGraphKernelNodeGetParams(node, &got)) != hipSuccess)) {
+    absorb_off(e);
+    return rc;
+  }
+  if (type != hipGraphNodeTypeKernel || got.func != head_fused_kernel()) return rc;
+  size_t total = 0;
+  if (!head_make_srcs(srcs_host, lens_host, n, R->head.hs, total)) return rc;
+  R->head.node = node;
+  R->head.cid = cid;
+  R->head.stream = st;
+  R->head.packed = packed;
+  R->head.image = image;
+  R->head.zero = zero;
+  R->head.zero_bytes = zero_bytes;
+  R->head.H2 = H2;
+  return rc;
+}
+
+extern "C" int gcm_rows_capture_node_count(gcm_stream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  unsigned long long cid = 0;
+  hipGraph_t graph = nullptr;
+  const hipGraphNode_t* deps = nullptr;
+  size_t nd = 0, nodes = 0;
+  if (hipStreamGetCaptureInfo_v2((hipStream_t)stream, &cs, &cid, &graph, &deps, &nd) != hipSuccess ||
+      cs != hipStreamCaptureStatusActive || hipGraphGetNodes(graph, nullptr, &nodes) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return (int)nodes;
 }

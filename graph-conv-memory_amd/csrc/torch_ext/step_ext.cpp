@@ -56,6 +56,7 @@ struct StepCfg {
   bool hops_bptt = true;  // forward-hop cached chains take gcm_dense_rows_bptt_cached_hops in their backward (A/B switch)
   bool merge_captured = true;   // lean cached steps captured back to back become one graph node (A/B switch)
   int merge_cap = 0;            // steps per such node (tests split a run with it); 0: the library's cap
+  bool absorb_head = true;      // ... and the rollout's head launch in front of step 0 is absorbed into it (A/B switch)
   int64_t P;
   bool has_distance = false;
   at::Tensor ws;   // scratch of the distance selectors
@@ -707,7 +708,7 @@ struct RowsFast {
   // the chain's run object (gcm_hip_run.h): inside a stream capture, cached lean steps that follow one another directly
   // are appended to ONE graph node.  Reset whenever the chain is re-armed or a step comes through the checked entry.
   void* mrun = nullptr;
-  int mrun_cap = 0;
+  int mrun_cap = 0, mrun_absorb = -1;
 
   RowsFast(const std::vector<std::pair<pybind11::object, pybind11::object>>& specs,
            const std::vector<pybind11::object>& hooks)
@@ -735,6 +736,24 @@ struct RowsFast {
       gcm_rows_run_set_cap(mrun, cap);
       mrun_cap = cap;
     }
+    set_absorb(cfg->absorb_head);
+    return mrun;
+  }
+  void set_absorb(bool on) {
+    if (mrun && (int)on != mrun_absorb) {
+      gcm_rows_run_set_absorb(mrun, on ? 1 : 0);
+      mrun_absorb = (int)on;
+    }
+  }
+  // the run object for the head launch of forward(x, None) (pack_params_head): the chain this head starts is armed
+  // right behind it.  nullptr with the switches off: the head is then gcm_dense_rows_head_fused exactly
+  void* head_run(bool on) {
+    if (!on) {
+      set_absorb(false);
+      return nullptr;
+    }
+    if (!mrun) mrun = gcm_rows_run_create();
+    set_absorb(true);
     return mrun;
   }
   std::pair<int, int> merge_stats() const {
@@ -742,6 +761,7 @@ struct RowsFast {
     if (mrun && !last_cached_eager) gcm_rows_run_stats(mrun, out);
     return {out[0], out[1]};
   }
+  int head_absorbed() const { return mrun && !last_cached_eager ? gcm_rows_run_absorbed(mrun) : 0; }
 
   bool hooks_registered() const {   // torch.nn.Module.__call__ has work to do: take the long way
     for (const auto& d : hook_dicts)
@@ -1749,8 +1769,11 @@ at::Tensor pack_params(const std::vector<at::Tensor>& ts) {
 // first six tensors are the GNN's (F, H1, H2 <= 64).  B > 0: the state DenseGCM._fresh_state carves - one allocation,
 // nodes [B,N,feats] | adj [B,N,N] | num_nodes [B] (int64) at 64-float paddings, independent tensors (own version
 // counters, no view relation).  The caller has checked: contiguous fp32 tensors on the current HIP device.
+// fast / absorb: the RowsFast of the configuration (or None) and DenseGCM.rows_absorb_head && rows_merge_captured - under
+// a stream capture the chain's run object then remembers this launch's node, and the chain's merged step node absorbs
+// it (gcm_hip_run_head.h).
 pybind11::tuple pack_params_head(const std::vector<at::Tensor>& ts, int F, int H1, int H2, bool want_image, int64_t B,
-                                 int64_t N, int64_t feats) {
+                                 int64_t N, int64_t feats, pybind11::object fast, bool absorb) {
   TORCH_CHECK(!ts.empty() && ts.size() <= 16, "pack_params_head: 1 .. 16 tensors");
   const at::Tensor& t0 = ts[0];
   std::vector<const float*> srcs;
@@ -1776,11 +1799,12 @@ pybind11::tuple pack_params_head(const std::vector<at::Tensor>& ts, int F, int H
     adj = alias_of(state, n_nodes, {B, N, N}, state.dtype());
     count = alias_of(state, (n_nodes + n_adj) / 2, {B}, caffe2::TypeMeta::Make<int64_t>());
   }
-  check(gcm_dense_rows_head_fused(srcs.data(), lens.data(), (int)ts.size(), packed.data_ptr<float>(),
-                                  want_image ? image.data_ptr<float>() : nullptr, F, H1, H2,
-                                  B > 0 ? state.data_ptr() : nullptr, sizeof(float) * (size_t)state_floats,
-                                  reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(t0.get_device()).stream())),
-        "gcm_dense_rows_head_fused");
+  void* run = fast.is_none() ? nullptr : fast.cast<RowsFast*>()->head_run(absorb && want_image && B > 0);
+  check(gcm_dense_rows_head_fused_run(run, srcs.data(), lens.data(), (int)ts.size(), packed.data_ptr<float>(),
+                                      want_image ? image.data_ptr<float>() : nullptr, F, H1, H2,
+                                      B > 0 ? state.data_ptr() : nullptr, sizeof(float) * (size_t)state_floats,
+                                      reinterpret_cast<gcm_stream_t>(c10::hip::getCurrentHIPStream(t0.get_device()).stream())),
+        "gcm_dense_rows_head_fused_run");
   hang_pack_node(packed, ts);
   auto opt = [](const at::Tensor& t) { return t.defined() ? pybind11::cast(t) : pybind11::object(pybind11::none()); };
   return pybind11::make_tuple(packed, opt(image), opt(nodes), opt(adj), opt(count));
@@ -2898,6 +2922,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_hops_bptt", [](StepCfg& c, bool on) { c.hops_bptt = on; })
       .def("set_col_cache", [](StepCfg& c, bool on) { c.col_cache = on; })
       .def("set_merge_captured", [](StepCfg& c, bool on, int cap) { c.merge_captured = on; c.merge_cap = cap; })
+      .def("set_absorb_head", [](StepCfg& c, bool on) { c.absorb_head = on; })
       .def("cached_launches", [](StepCfg& c, int B) {   // launches per cached step (0: no cached form)
         return gcm_dense_rows_cached_launches(c.descs.empty() ? nullptr : c.descs.data(), (int)c.descs.size(),
                                               c.has_bias | c.cached_flags, B, c.N, c.F, c.H1, c.H2);
@@ -2919,6 +2944,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("rolled_steps", [](RowsFast& f) { return f.rolled_steps; })
       .def("col_steps", [](RowsFast& f) { return f.col_steps; })
       .def("merge_stats", &RowsFast::merge_stats)
+      .def("head_absorbed", &RowsFast::head_absorbed)
       .def("has_chain", [](RowsFast& f) { return f.node != nullptr || f.dxc != nullptr; });
   pybind11::class_<LearnedCfg>(m, "LearnedCfg")
       .def(pybind11::init<int, int, int, int, int, int, int, double, double, double>())
@@ -2934,7 +2960,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("steps", &LearnedChain::steps);
   m.def("learned_step2", &learned_step2);
   m.def("pack_params", &pack_params);
-  m.def("pack_params_head", &pack_params_head);
+  m.def("pack_params_head", &pack_params_head, pybind11::arg("tensors"), pybind11::arg("F"), pybind11::arg("H1"),
+        pybind11::arg("H2"), pybind11::arg("want_image"), pybind11::arg("B"), pybind11::arg("N"), pybind11::arg("feats"),
+        pybind11::arg("fast") = pybind11::none(), pybind11::arg("absorb") = false);
   pybind11::class_<LearnedFast>(m, "LearnedFast")
       .def(pybind11::init<const std::vector<std::pair<pybind11::object, pybind11::object>>&,
                           const std::vector<pybind11::object>&, pybind11::object>())

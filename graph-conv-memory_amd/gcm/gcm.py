@@ -306,6 +306,12 @@ class DenseGCM(torch.nn.Module):
         # GCM_MERGE_CAPTURED=0): one node per step (A/B); the same bits either way.  Read when a chain is armed
         self.rows_merge_captured = os.environ.get("GCM_MERGE_CAPTURED", "1") == "1"
         self.rows_merge_cap = None   # tests: steps per merged node (None: the library's cap)
+        # True: in such a capture the head launch of forward(x, None) (rows_fused_head) that sits directly in front of
+        # step 0 is absorbed into the merged node: the node is added on the head's dependencies, runs the kernel's
+        # fresh-state form - which writes the packed vector, the weight image and the whole state itself - and the head's
+        # node is destroyed ("the head absorbed"): one dependent launch less per replay.  False (env
+        # GCM_ABSORB_HEAD=0): the head stays a node (A/B); the same bits either way.  Read when a chain is armed
+        self.rows_absorb_head = os.environ.get("GCM_ABSORB_HEAD", "1") == "1"
         self._head_ready = None   # (cfg, grad mode) of the packed vector forward(x, None) has just built with the state
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
@@ -357,16 +363,21 @@ class DenseGCM(torch.nn.Module):
                 n += cfg._rows_fast.steps()
         return n
 
-    def merge_stats(self):
+    def merge_stats(self, head=False):
         """What became of this module's cached steps in the stream capture seen last: {"nodes": graph nodes they were
         launched as, "merged_steps": steps appended to an existing node instead (rows_merge_captured)}.  Both 0 after
-        an eager step."""
-        nodes = merged = 0
+        an eager step.  head=True: also "head_absorbed", the head launches of forward(x, None) whose node a merged node
+        took the place of (rows_absorb_head)."""
+        nodes = merged = absorbed = 0
         for cfg in self._cfg_cache.values():
             if cfg is not False and cfg._rows_fast is not None:
                 a, b = cfg._rows_fast.merge_stats()
                 nodes, merged = nodes + a, merged + b
-        return {"nodes": nodes, "merged_steps": merged}
+                absorbed += cfg._rows_fast.head_absorbed()
+        out = {"nodes": nodes, "merged_steps": merged}
+        if head:
+            out["head_absorbed"] = absorbed
+        return out
 
     def learned_fast_steps(self):
         """Number of LearnedEdge steps that went from __call__ straight into the C++ host path (LearnedFast)."""
@@ -758,8 +769,12 @@ class DenseGCM(torch.nn.Module):
                 # ... and the weight image, and a fresh state, out of the same launch
                 want_image = cfg.learned_sel is None and max(cfg.F, cfg.H1, cfg.H2) <= 64
                 B, N, F = fresh[:3] if fresh is not None else (0, 0, 0)
+                # (under a capture the chain's run object remembers the launch: its merged step node may absorb it)
+                absorb = bool(fresh is not None and self.rows_absorb_head and self.rows_merge_captured
+                              and self.rows_merge_cap != 1 and cfg.rows_ok and cfg.learned_sel is None)
                 packed, image, *state = _ops._ext.module().pack_params_head(
-                    list(tensors), cfg.F, cfg.H1, cfg.H2, want_image, B, N, F)
+                    list(tensors), cfg.F, cfg.H1, cfg.H2, want_image, B, N, F,
+                    cfg.rows_fast(self) if absorb else cfg._rows_fast, absorb)
                 if fresh is not None:
                     fresh[3].extend(state)
             else:
@@ -876,6 +891,7 @@ class DenseGCM(torch.nn.Module):
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
                 cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
                 cfg._cpp.set_merge_captured(bool(self.rows_merge_captured), int(self.rows_merge_cap or 0))
+                cfg._cpp.set_absorb_head(bool(self.rows_absorb_head))
             image = self._packed_cache[5]
             if image is not None and self._packed_cache[1] is root:
                 fast.set_head_image(root, image)   # (the first cached step takes it iff it is armed with this vector)

@@ -6,7 +6,9 @@
            step nodes must cost what it cost before the switch existed
 
 One JSON line per form: us per replay, us per step, and merge_stats() where the module has it (so the same file runs
-on a tree from before the switch).  --label names the leg; GCM_MERGE_CAPTURED=0 is the switch-off leg.  Dev tool."""
+on a tree from before the switch).  --label names the leg; GCM_MERGE_CAPTURED=0 is the switch-off leg, and
+GCM_ABSORB_HEAD=0 the leg that merges the steps but keeps the rollout's head launch a node of its own (merge_stats
+then reports head_absorbed: 0).  Dev tool."""
 import argparse
 import json
 import os
@@ -44,7 +46,9 @@ def measure(form, dev, replays, repeats):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         loop()
-    stats = mem.merge_stats() if hasattr(mem, "merge_stats") else None
+    stats = None
+    if hasattr(mem, "merge_stats"):   # (head=True: trees that can absorb the head launch say whether they did)
+        stats = mem.merge_stats(head=True) if hasattr(mem, "rows_absorb_head") else mem.merge_stats()
     for _ in range(20):
         graph.replay()
     torch.cuda.synchronize()
