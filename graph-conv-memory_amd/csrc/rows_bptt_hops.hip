@@ -16,6 +16,10 @@
 //
 // - what k_bptt_cached_graph accumulates row by row from live / coef / l_cur, summed over rows instead of over steps.
 //
+// Two kernels compute it.  k_bptt_hops_graph_fold (further down, with its own description) is what
+// gcm_dense_rows_bptt_cached_hops launches; k_bptt_hops_graph, described here, is the form before the hop sum was folded
+// into the product and stays behind gcm_dense_rows_bptt_cached_hops_unfolded for the A/B.
+//
 // One workgroup of eight waves per graph.  Wave w owns steps 16 w .. 16 w + 15 and cache rows 16 w .. 16 w + 15: lanes
 // 0-31 take the even one of a pair, lanes 32-63 the odd one, element q = lane & 31 - the operand layout of
 // v_mfma_f32_32x32x2_f32 (k = the half), so D2, the v section and the cache rows go from global memory into the
@@ -228,16 +232,287 @@ __global__ __launch_bounds__(512) void k_bptt_hops_graph(StepTable tab, HopsTabl
   STAMP(6);   // summed in wave order, the graph's slab stored
 }
 
+// ---- the folded form ----------------------------------------------------------------------------------------------------
+// The hop sum commutes with the product, so U is never formed:
+//
+//     D2s[j,:]   = sum over hops h > 0 (ascending) with a step s of this call at cur[s] = j + h:  D2[s,:]
+//                  (+ D2[s',:] with self, s' the step of this call that wrote row j)
+//     G1pre[j,:] = D2s[j,:] . W_rel2 + D2[s',:] . W_root2                       one 32 x 32 tile, K = 2 H2
+//
+// and the waves take ROLES instead of sixteen steps and sixteen rows each:
+//   waves 0-3  (layer 2)  wave w owns steps 32 w .. 32 w + 31: their mx / g_mx / v loads, D2 -> LDS, barrier, then the
+//              dW2 / db2 partials of those steps (32 MFMAs) from the registers, beside the layer-1 waves' work
+//   waves 4-7  (layer 1)  wave 4 + t owns cache rows 32 t .. 32 t + 31: their cH / cA / cX loads, both weight tiles and
+//              the row -> step map entries of its sources (byte loads of the kernel arguments: no map in LDS) are
+//              issued before the barrier.  Behind it the A operand of the tile product is FORMED WHILE IT IS READ from
+//              sD2: lane (q, half) owns row 32 t + q and the K entries 2 kk + half, which sD2 keeps contiguous
+//              ([step][half][kk], 36 floats a step: four ds_read_b128 per source step, conflict-free), a source that
+//              does not exist reads the zero row 128 - no select, no dependent read.  32 MFMAs leave lane (q, half)
+//              holding G1pre[32 t + acc_row(r, half)][q], r = 0..15: times act1' that IS the A operand of the outer
+//              products G1^T . cA and G1^T . cX, MFMA r pairing row acc_row(r, 0) with row acc_row(r, 1) (any pairing
+//              of rows is a valid K order), so the lane loads its cH / cA / cX rows by that pairing and the tile goes
+//              into dW1 / db1 (32 MFMAs) without a trip through LDS.
+// One SIMD holds wave w and wave w + 4: a layer-2 and a layer-1 wave, 32 + 64 of the graph's 384 MFMAs.  Two barriers
+// (D2 in LDS; the partial slabs in LDS) where the unfolded form has four; the partial slabs have a place of their own
+// (four layer-1 partials of dW1 | db1, four layer-2 partials of dW2 | db2: each element is a sum of four, in wave order).
+// LDS: 129 * 36 + 4 * 2080 + 4 * (64 H2 + H2) floats <= 85,136 B.
+#ifdef GCM_STAMPS
+#define STAMP_L1(i)                                                                  \
+  do {                                                                               \
+    if (blockIdx.x == 0 && threadIdx.x == 256) {                                     \
+      unsigned long long t_;                                                         \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
+      g_stamps[i] = t_;                                                              \
+    }                                                                                \
+  } while (0)
+#else
+#define STAMP_L1(i)
+#endif
+
+__global__ __launch_bounds__(512) void k_bptt_hops_graph_fold(StepTable tab, HopsTable ht, int T, int rows_written,
+                                                              long gmx_sb, long gmx_sh, const float* __restrict__ w_rel2,
+                                                              const float* __restrict__ w_root2, int act1, int act2,
+                                                              unsigned o_v, const float* __restrict__ cH,
+                                                              const float* __restrict__ cA, const float* __restrict__ cX,
+                                                              float* __restrict__ slabs, int N, int H2) {
+  constexpr int NMAX = 128, H1 = 32, F = 32, DF = 36, NR = 4;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, q = lane & 31, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool layer2 = wave < NR;
+  const int act1_v = gcm_vgpr(act1), act2_v = gcm_vgpr(act2);
+  extern __shared__ __attribute__((aligned(16))) float sFold[];
+  float* sD2 = sFold;                        // [NMAX + 1][DF]: D2[s][o] at s DF + 16 (o & 1) + (o >> 1); row NMAX: zeros
+  float* sPart = sD2 + (NMAX + 1) * DF;      // NR partials of dW1 | db1, then NR partials of dW2 | db2
+  const int P1 = 2 * H1 * F + H1, P2 = 2 * H2 * H1 + H2;
+  STAMP(0);
+  STAMP_L1(16);
+
+  float mxv[16], gv[16], va[16], vb[16];     // layer 2: the wave's 16 pairs of steps
+  float hr[16], ar[16], xr[16], wr[16], wt[16];   // layer 1: the tile's rows by the accumulator's pairing; the weight tiles
+  int src[5];                                // layer 1: the sD2 row of each source of row 32 t + q (hops ascending, own step)
+  const int t = wave - NR;
+
+  // ---- stage: every load of this wave, issued before the first wait ---------------------------------------------------
+  if (layer2) {
+    const int oq = q < H2 ? q : H2 - 1;
+    // (the steps' pointers as scalar loads of the arguments, four pairs of steps per wait, then a select per half: see
+    //  k_bptt_hops_graph.  The selected pointer is cast to the GLOBAL address space: as a generic pointer it makes flat
+    //  loads, which count as LDS traffic too and are waited for all at once)
+    typedef const float __attribute__((address_space(1))) * gptr;
+#pragma unroll
+    for (int i4 = 0; i4 < 16; i4 += 4) {
+      unsigned long long ps[4][2], pg[4][2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int s = min(32 * wave + 2 * (i4 + k) + h, T - 1);   // (clamped: T >= 1)
+          ps[k][h] = (unsigned long long)tab.saved[s];
+          pg[k][h] = (unsigned long long)tab.gmx[s];
+        }
+      asm volatile("" : "+s"(ps[0][0]), "+s"(ps[0][1]), "+s"(ps[1][0]), "+s"(ps[1][1]), "+s"(ps[2][0]), "+s"(ps[2][1]),
+                        "+s"(ps[3][0]), "+s"(ps[3][1]), "+s"(pg[0][0]), "+s"(pg[0][1]), "+s"(pg[1][0]), "+s"(pg[1][1]),
+                        "+s"(pg[2][0]), "+s"(pg[2][1]), "+s"(pg[3][0]), "+s"(pg[3][1]));
+      // (per pair mx, g_mx, then v: the waits in front of D2 are counted, so D2 of a pair starts under the later loads.
+      //  mx / g_mx of ALL pairs first was measured and not kept: DESIGN 3.2)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i4 + k;
+        const gptr sv = (gptr)(half ? ps[k][1] : ps[k][0]);
+        const gptr gp = (gptr)(half ? pg[k][1] : pg[k][0]);
+        mxv[i] = sv[(size_t)b * H2 + oq];
+        gv[i] = gp[(long)b * gmx_sb + (long)oq * gmx_sh];
+        va[i] = sv[o_v + (size_t)b * 64 + q];          // agg2
+        vb[i] = sv[o_v + (size_t)b * 64 + 32 + q];     // h1cur
+      }
+    }
+  } else {
+    const float* hb = cH + (size_t)b * N * 32;   // (uniform bases, one 32-bit offset per lane and row)
+    const float* ab = cA + (size_t)b * N * 32;
+    const float* xb = cX + (size_t)b * N * 32;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int j = 32 * t + gcm_fused::acc_row(r, half);
+      const unsigned rj = (unsigned)min(j, rows_written - 1) * 32u + (unsigned)q;   // (clamped: 1 <= rows_written <= N)
+      hr[r] = hb[rj];
+      ar[r] = ab[rj];
+      xr[r] = xb[rj];
+    }
+    // B operands of MFMA kk: W[2 kk + half][q]
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      const unsigned wo = (unsigned)min(2 * kk + half, H2 - 1) * H1 + (unsigned)q;
+      wr[kk] = w_rel2[wo];
+      wt[kk] = w_root2[wo];
+    }
+    const int j = 32 * t + q;   // (<= 127)
+    int mv[5];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int jh = j + ht.hop[k];
+      mv[k] = ht.row2step[(k < ht.n_hops && jh < NMAX) ? jh : j];
+    }
+    mv[4] = ht.row2step[j];
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int jh = j + ht.hop[k];
+      src[k] = (k < ht.n_hops && jh < NMAX && mv[k] < T) ? mv[k] : NMAX;   // (0xff: no step wrote that row)
+    }
+    src[4] = mv[4] < T ? mv[4] : NMAX;
+  }
+  asm volatile("" ::: "memory");
+  STAMP(1);   // every load issued
+  STAMP_L1(17);
+
+  // ---- layer 2: D2 of the wave's steps into LDS (kept in registers for dW2 / db2); layer 1: the zero row ---------------
+  if (layer2) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int s = 32 * wave + 2 * i + half;
+      const bool on = s < T;
+      const float d2 = (on && q < H2) ? gv[i] * gcm_act_grad_sel(mxv[i], act2_v) : 0.f;
+      sD2[s * DF + 16 * (q & 1) + (q >> 1)] = d2;
+      gv[i] = d2;
+      va[i] = on ? va[i] : 0.f;
+      vb[i] = on ? vb[i] : 0.f;
+    }
+  } else if (tid - 64 * NR < DF) {
+    sD2[NMAX * DF + tid - 64 * NR] = 0.f;
+  }
+  __syncthreads();
+  STAMP(2);   // D2 in LDS; barrier
+  STAMP_L1(18);
+
+  if (layer2) {
+    // ---- dW2 / db2 partials straight from the registers --------------------------------------------------------------
+    f32x16 aR2, aT2;   // dW_rel2 [o][k], dW_root2 [o][k]
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { aR2[r] = 0.f; aT2[r] = 0.f; }
+    float db2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      db2 += gv[i];
+      aR2 = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[i], va[i], aR2, 0, 0, 0);   // d2 (x) agg2
+      aT2 = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[i], vb[i], aT2, 0, 0, 0);   // d2 (x) h1cur
+    }
+    STAMP(3);   // dW2 / db2 partials
+    float* mine = sPart + NR * P1 + wave * P2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = gcm_fused::acc_row(r, half);
+      if (i < H2) {
+        mine[i * 32 + q] = aR2[r];
+        mine[H2 * H1 + i * 32 + q] = aT2[r];
+      }
+    }
+    const float s2 = gcm_xor32_add(db2);
+    if (lane < H2) mine[2 * H2 * H1 + lane] = s2;
+  } else {
+    // ---- the tile's A operands, formed from sD2 while read: rel = the sources' sum, root = the own step ---------------
+    f32x16 aR, aT;   // dW_rel1 [h][f], dW_root1 [h][f]
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { aR[r] = 0.f; aT[r] = 0.f; }
+    float db1 = 0.f;
+    if (32 * t < rows_written) {   // (a tile without a written row: G1 = 0)
+      float4 own[4], sum[4];
+      {
+        const float4* p = reinterpret_cast<const float4*>(sD2 + src[4] * DF + 16 * half);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) own[c] = p[c];
+      }
+      // (a hop beyond n_hops reads the zero row like a source that does not exist: no branch between the reads)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float4* p = reinterpret_cast<const float4*>(sD2 + src[k] * DF + 16 * half);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float4 v = p[c];
+          if (k == 0) {
+            sum[c] = v;
+          } else {
+            sum[c].x += v.x; sum[c].y += v.y; sum[c].z += v.z; sum[c].w += v.w;
+          }
+        }
+      }
+      if (ht.self != 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          sum[c].x += own[c].x; sum[c].y += own[c].y; sum[c].z += own[c].z; sum[c].w += own[c].w;
+        }
+      }
+      STAMP_L1(19);   // the A operands read and summed
+      // ---- G1pre = D2s . W_rel2 + D2 . W_root2: K = 2 H2 into one accumulator ------------------------------------------
+      f32x16 aG;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) aG[r] = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float a4[4] = {sum[c].x, sum[c].y, sum[c].z, sum[c].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int kk = 4 * c + e;
+          aG = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], 2 * kk + half < H2 ? wr[kk] : 0.f, aG, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float a4[4] = {own[c].x, own[c].y, own[c].z, own[c].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int kk = 4 * c + e;
+          aG = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], 2 * kk + half < H2 ? wt[kk] : 0.f, aG, 0, 0, 0);
+        }
+      }
+      STAMP_L1(20);   // the tile product
+      // ---- G1 = G1pre * act1'(cH); the accumulator's register r is the A operand of outer product r --------------------
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool written = 32 * t + gcm_fused::acc_row(r, half) < rows_written;
+        const float g1 = written ? aG[r] * gcm_act_grad_sel(hr[r], act1_v) : 0.f;
+        db1 += g1;
+        aR = __builtin_amdgcn_mfma_f32_32x32x2f32(g1, written ? ar[r] : 0.f, aR, 0, 0, 0);
+        aT = __builtin_amdgcn_mfma_f32_32x32x2f32(g1, written ? xr[r] : 0.f, aT, 0, 0, 0);
+      }
+    }
+    STAMP_L1(21);   // G1, dW1 / db1 partials
+    float* mine = sPart + t * P1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = gcm_fused::acc_row(r, half);
+      mine[i * 32 + q] = aR[r];
+      mine[H1 * F + i * 32 + q] = aT[r];
+    }
+    const float s1 = gcm_xor32_add(db1);
+    if (lane < 32) mine[2 * H1 * F + lane] = s1;
+  }
+  __syncthreads();
+  STAMP(5);   // the partial slabs in LDS; barrier
+  STAMP_L1(22);
+
+  // ---- one slab per graph, the layout of k_bptt_hops_graph: four partials per element, in wave order ------------------
+  float* slab = slabs + (size_t)b * (P1 + P2);
+  for (int e = tid; e < P1 + P2; e += 512) {
+    const float* p = e < P1 ? sPart + e : sPart + NR * P1 + (e - P1);
+    const int st = e < P1 ? P1 : P2;
+    float t_ = 0.f;
+#pragma unroll
+    for (int w = 0; w < NR; ++w) t_ += p[w * st];
+    slab[e] = t_;
+  }
+  STAMP(6);   // summed in wave order, the graph's slab stored
+  STAMP_L1(23);
+}
+
 }  // namespace gcm_rows
 
-extern "C" int gcm_dense_rows_bptt_cached_hops(const float* const* saved_host, const float* const* gmx_host, int n_steps,
-                                               long gmx_stride_b, long gmx_stride_h, const float* params, int has_bias,
-                                               int act1, int act2, const float* cache_nodes, const float* cache_h1,
-                                               const float* cache_agg1, const uint8_t* cur_host,
-                                               const gcm_selector_desc* selectors, int n_selectors, int rows_written,
-                                               const float* g_params_prev, float* g_params, void* workspace,
-                                               size_t workspace_bytes, int B, int N, int F, int H1, int H2,
-                                               gcm_stream_t stream) {
+// the entries' body; fold: k_bptt_hops_graph_fold, else k_bptt_hops_graph (same arguments, same slab)
+static int launch_bptt_hops(bool fold, const float* const* saved_host, const float* const* gmx_host, int n_steps,
+                            long gmx_stride_b, long gmx_stride_h, const float* params, int has_bias, int act1, int act2,
+                            const float* cache_nodes, const float* cache_h1, const float* cache_agg1,
+                            const uint8_t* cur_host, const gcm_selector_desc* selectors, int n_selectors, int rows_written,
+                            const float* g_params_prev, float* g_params, void* workspace, size_t workspace_bytes, int B,
+                            int N, int F, int H1, int H2, gcm_stream_t stream) {
   GCM_REQUIRE(saved_host && gmx_host && params && g_params && workspace && cache_nodes && cache_h1 && cache_agg1 && cur_host);
   GCM_REQUIRE(n_steps > 0 && B > 0 && (selectors || n_selectors == 0));
   if (F != 32 || H1 != 32 || H2 <= 0 || H2 > 32 || N <= 0 || N > 128 || n_steps > GCM_ROWS_MAX_STEPS) return GCM_EUNSUPPORTED;
@@ -275,16 +550,52 @@ extern "C" int gcm_dense_rows_bptt_cached_hops(const float* const* saved_host, c
   if (workspace_bytes < sizeof(float) * Pg * (size_t)B) return GCM_EWORKSPACE;
   const gcm_rows::CachedLayout lay = gcm_rows::make_cached_layout(B, N, H1, H2);
   if (lay.total >= ((size_t)1 << 31)) return GCM_EUNSUPPORTED;
-  const size_t stage = sizeof(float) * (128 * 33 + 128 * 65 + 128), out = sizeof(float) * 8 * Pg;
-  const size_t lds = stage > out ? stage : out;
   float* slabs = (float*)workspace;
   const float* w_rel2 = params + 2 * (size_t)H1 * F + H1;
   const float* w_root2 = w_rel2 + (size_t)H2 * H1;
-  gcm_allow_dynamic_lds((const void*)gcm_rows::k_bptt_hops_graph, lds);
-  hipLaunchKernelGGL(gcm_rows::k_bptt_hops_graph, dim3(B), dim3(512), lds, (hipStream_t)stream, tab, ht, n_steps,
-                     rows_written, gmx_stride_b, gmx_stride_h, w_rel2, w_root2, act1, act2, (unsigned)lay.o_v, cache_h1,
-                     cache_agg1, cache_nodes, slabs, N, H2);
+  if (fold) {
+    const size_t lds = sizeof(float) * (129 * 36 + 4 * Pg);   // D2 and its zero row, 4 + 4 partial slabs
+    gcm_allow_dynamic_lds((const void*)gcm_rows::k_bptt_hops_graph_fold, lds);
+    hipLaunchKernelGGL(gcm_rows::k_bptt_hops_graph_fold, dim3(B), dim3(512), lds, (hipStream_t)stream, tab, ht, n_steps,
+                       rows_written, gmx_stride_b, gmx_stride_h, w_rel2, w_root2, act1, act2, (unsigned)lay.o_v, cache_h1,
+                       cache_agg1, cache_nodes, slabs, N, H2);
+  } else {
+    const size_t stage = sizeof(float) * (128 * 33 + 128 * 65 + 128), out = sizeof(float) * 8 * Pg;
+    const size_t lds = stage > out ? stage : out;
+    gcm_allow_dynamic_lds((const void*)gcm_rows::k_bptt_hops_graph, lds);
+    hipLaunchKernelGGL(gcm_rows::k_bptt_hops_graph, dim3(B), dim3(512), lds, (hipStream_t)stream, tab, ht, n_steps,
+                       rows_written, gmx_stride_b, gmx_stride_h, w_rel2, w_root2, act1, act2, (unsigned)lay.o_v, cache_h1,
+                       cache_agg1, cache_nodes, slabs, N, H2);
+  }
   const int rc = gcm_launch_status();
   if (rc) return rc;
   return gcm_sum_slabs_acc(slabs, B, (int)Pg, g_params_prev, g_params, stream);
+}
+
+#define GCM_BPTT_HOPS_ARGS                                                                                              \
+  saved_host, gmx_host, n_steps, gmx_stride_b, gmx_stride_h, params, has_bias, act1, act2, cache_nodes, cache_h1,       \
+      cache_agg1, cur_host, selectors, n_selectors, rows_written, g_params_prev, g_params, workspace, workspace_bytes, \
+      B, N, F, H1, H2, stream
+
+extern "C" int gcm_dense_rows_bptt_cached_hops(const float* const* saved_host, const float* const* gmx_host, int n_steps,
+                                               long gmx_stride_b, long gmx_stride_h, const float* params, int has_bias,
+                                               int act1, int act2, const float* cache_nodes, const float* cache_h1,
+                                               const float* cache_agg1, const uint8_t* cur_host,
+                                               const gcm_selector_desc* selectors, int n_selectors, int rows_written,
+                                               const float* g_params_prev, float* g_params, void* workspace,
+                                               size_t workspace_bytes, int B, int N, int F, int H1, int H2,
+                                               gcm_stream_t stream) {
+  return launch_bptt_hops(true, GCM_BPTT_HOPS_ARGS);
+}
+
+extern "C" int gcm_dense_rows_bptt_cached_hops_unfolded(const float* const* saved_host, const float* const* gmx_host,
+                                                        int n_steps, long gmx_stride_b, long gmx_stride_h,
+                                                        const float* params, int has_bias, int act1, int act2,
+                                                        const float* cache_nodes, const float* cache_h1,
+                                                        const float* cache_agg1, const uint8_t* cur_host,
+                                                        const gcm_selector_desc* selectors, int n_selectors,
+                                                        int rows_written, const float* g_params_prev, float* g_params,
+                                                        void* workspace, size_t workspace_bytes, int B, int N, int F,
+                                                        int H1, int H2, gcm_stream_t stream) {
+  return launch_bptt_hops(false, GCM_BPTT_HOPS_ARGS);
 }

@@ -54,6 +54,7 @@ struct StepCfg {
   int cached_flags = 0;   // extra has_bias bits of the cached step only (GCM_STEP_TWO_LAUNCH: the A/B of tests / tools)
   bool col_cache = true;  // chains whose selectors write column cur take gcm_dense_rows_step_colcache (A/B switch)
   bool hops_bptt = true;  // forward-hop cached chains take gcm_dense_rows_bptt_cached_hops in their backward (A/B switch)
+  bool hops_fold = true;  // ... with the hop sum folded into its products (off: ..._hops_unfolded, the kernel before; A/B switch)
   bool merge_captured = true;   // lean cached steps captured back to back become one graph node (A/B switch)
   int merge_cap = 0;            // steps per such node (tests split a run with it); 0: the library's cap
   bool absorb_head = true;      // ... and the rollout's head launch in front of step 0 is absorbed into it (A/B switch)
@@ -277,6 +278,7 @@ struct RowsChainNode : public torch::autograd::Node {
   at::Tensor cH, cA, cX;        // the caches of the chain's cached steps
   bool many_rows = false;       // a DenseEdge selector: every row <= cur is live (GCM_BPTT_MANY_ROWS)
   bool hops_bptt = true;        // StepCfg::hops_bptt when the chain was armed
+  bool hops_fold = true;        // StepCfg::hops_fold when the chain was armed
   std::vector<gcm_selector_desc> descs;   // ... and the selectors their live rows follow from (dx of cached steps)
   std::vector<Rec> recs;   // the recorded steps, in chain order
   at::Tensor packed;       // the packed parameter vector, detached (the kernel re-reads the weights)
@@ -449,7 +451,8 @@ struct RowsChainNode : public torch::autograd::Node {
                                       ? GCM_STEP_FOUR_WAVES : 0;
       int hops_rc = GCM_EUNSUPPORTED;
       if (hops)
-        hops_rc = gcm_dense_rows_bptt_cached_hops(c.sv.data(), c.gm.data(), n, (long)c.sb, (long)c.sh,
+        hops_rc = (hops_fold ? gcm_dense_rows_bptt_cached_hops : gcm_dense_rows_bptt_cached_hops_unfolded)(
+                                                  c.sv.data(), c.gm.data(), n, (long)c.sb, (long)c.sh,
                                                   packed.data_ptr<float>(), has_bias, act1, act2, cX.data_ptr<float>(),
                                                   cH.data_ptr<float>(), cA.data_ptr<float>(), c.cur.data(),
                                                   descs.empty() ? nullptr : descs.data(), (int)descs.size(), rows_written,
@@ -838,6 +841,7 @@ struct RowsFast {
       TORCH_CHECK(packed.numel() >= node->P, "rows step: packed parameter vector too short");
       for (const auto& d : cfg->descs) node->many_rows = node->many_rows || d.kind == GCM_SEL_DENSE;
       node->hops_bptt = cfg->hops_bptt;
+      node->hops_fold = cfg->hops_fold;
       node->set_next_edges(torch::autograd::collect_next_edges(packed));
       if (dx_ == 1) {
         dx_mode = true;
@@ -1967,6 +1971,7 @@ struct RowsRolloutNode : public torch::autograd::Node {
   // from empty graphs, no resets, T <= N <= 128 (every row below T written by step t = row t, every hop a row of the
   // same graph): gcm_dense_rows_bptt_cached_hops with the trivial table
   bool hop_rows = false;
+  bool hops_fold = true;   // StepCfg::hops_fold
   std::vector<gcm_selector_desc> descs;
   variable_list apply(variable_list&& grads) override {
     variable_list out(1);
@@ -1993,7 +1998,8 @@ struct RowsRolloutNode : public torch::autograd::Node {
     if (hop_rows) {
       std::vector<uint8_t> cur((size_t)T);
       for (int64_t t = 0; t < T; ++t) cur[t] = (uint8_t)t;
-      hops_rc = gcm_dense_rows_bptt_cached_hops(sv.data(), gm.data(), (int)T, (long)g.stride(1), (long)g.stride(2),
+      hops_rc = (hops_fold ? gcm_dense_rows_bptt_cached_hops : gcm_dense_rows_bptt_cached_hops_unfolded)(
+                                                sv.data(), gm.data(), (int)T, (long)g.stride(1), (long)g.stride(2),
                                                 packed.data_ptr<float>(), has_bias, act1, act2, cX.data_ptr<float>(),
                                                 cH.data_ptr<float>(), cA.data_ptr<float>(), cur.data(),
                                                 descs.empty() ? nullptr : descs.data(), (int)descs.size(), (int)T, nullptr,
@@ -2101,6 +2107,7 @@ pybind11::object rows_rollout_tp(int64_t cfg_handle, const at::Tensor& packed, c
     node->version = node->vc.current_version();
     node->hop_rows = cfg->hops_bptt && !euclid && !with_reset && T <= N && T <= 128;
     if (node->hop_rows) node->descs = cfg->descs;
+    node->hops_fold = cfg->hops_fold;
     node->set_next_edges(torch::autograd::collect_next_edges(packed));
     torch::autograd::create_gradient_edge(mx_all, node);
   }
@@ -2920,6 +2927,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("update_descs", &StepCfg::update_descs)
       .def("set_cached_flags", [](StepCfg& c, int f) { c.cached_flags = f; })
       .def("set_hops_bptt", [](StepCfg& c, bool on) { c.hops_bptt = on; })
+      .def("set_hops_fold", [](StepCfg& c, bool on) { c.hops_fold = on; })
       .def("set_col_cache", [](StepCfg& c, bool on) { c.col_cache = on; })
       .def("set_merge_captured", [](StepCfg& c, bool on, int cap) { c.merge_captured = on; c.merge_cap = cap; })
       .def("set_absorb_head", [](StepCfg& c, bool on) { c.absorb_head = on; })

@@ -36,6 +36,8 @@ RESET_PROTOTYPES = _abi.prototypes(_RESET_HEADER)
 GIN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gin.h"))
 # and the section from gcm_hip_bptt_hops.h (the GEMM-form backward of forward-hop cached chains)
 BPTT_HOPS_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_bptt_hops.h"))
+# and the section from gcm_hip_bptt_hops_unfolded.h (that backward before the hop sum was folded into its products: the A/B)
+BPTT_HOPS_UNFOLDED_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_bptt_hops_unfolded.h"))
 # and the section from gcm_hip_resgated.h (ResGatedGraphConv / DenseResGatedGraphConv)
 RESGATED_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_resgated.h"))
 # and the section from gcm_hip_gated.h (GatedGraphConv / DenseGatedGraphConv)
@@ -119,6 +121,7 @@ def lib():
         bind(handle, RESET_PROTOTYPES)
         bind(handle, GIN_PROTOTYPES)
         bind(handle, BPTT_HOPS_PROTOTYPES)
+        bind(handle, BPTT_HOPS_UNFOLDED_PROTOTYPES)
         bind(handle, RESGATED_PROTOTYPES)
         bind(handle, GATED_PROTOTYPES)
         bind(handle, TAG_PROTOTYPES)

@@ -293,6 +293,11 @@ class DenseGCM(torch.nn.Module):
         # the records' live lists not read).  False (env GCM_BPTT_HOPS=0): k_bptt_cached_graph, which every other chain
         # keeps (A/B); read when a chain is armed / a rollout starts
         self.rows_hops_bptt = os.environ.get("GCM_BPTT_HOPS", "1") == "1"
+        # True: that GEMM form sums the D2 rows of a row's hop sources BEFORE the layer-2 product and multiplies once
+        # (k_bptt_hops_graph_fold: no U image in LDS, the product's accumulator feeds dW1 from the registers).  False
+        # (env GCM_BPTT_HOPS_FOLD=0): the kernel before, U through LDS and a gather (A/B); the gradients of the two
+        # differ by re-ordered float32 sums
+        self.rows_hops_fold = os.environ.get("GCM_BPTT_HOPS_FOLD", "1") == "1"
         # True: the head of a chain - the packed parameter vector, the cached step's weight image and, from hidden = None,
         # the zero state - is ONE launch (csrc/head_fused.hip) instead of a fill, a cat and the image kernel one behind the
         # other in front of step 0.  Taken when the six GNN tensors (and the edge network's) are all present, contiguous
@@ -890,6 +895,7 @@ class DenseGCM(torch.nn.Module):
                     | (0 if self.rows_lean_step else _hip.STEP_NOT_LEAN))
                 cfg._cpp.set_col_cache(bool(self.rows_col_cache))
                 cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
+                cfg._cpp.set_hops_fold(bool(self.rows_hops_fold))
                 cfg._cpp.set_merge_captured(bool(self.rows_merge_captured), int(self.rows_merge_cap or 0))
                 cfg._cpp.set_absorb_head(bool(self.rows_absorb_head))
             image = self._packed_cache[5]
@@ -1134,6 +1140,7 @@ class DenseGCM(torch.nn.Module):
                 if cfg.cpp_handle():
                     flags = self._flag_word(obs.device)
                     cfg._cpp.set_hops_bptt(bool(self.rows_hops_bptt))
+                    cfg._cpp.set_hops_fold(bool(self.rows_hops_fold))
                     if reset is None:
                         r = _ops._ext.module().rows_rollout_tp(cfg.cpp_handle(), self._packed_params(cfg, head=True),
                                                                obs, flags)

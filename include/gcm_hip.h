@@ -949,6 +949,9 @@ int gcm_dense_rows_bptt_cached(const float* const* saved_host, const float* cons
 /* ... and its GEMM form for chains of forward temporal hops with host-known rows (cfg2; csrc/rows_bptt_hops.hip).
  * Declared in gcm_hip_bptt_hops.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_bptt_hops.h"
+/* ... and the kernel that entry launched before the hop sum was folded into its products, kept for the A/B.
+ * Declared in gcm_hip_bptt_hops_unfolded.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_bptt_hops_unfolded.h"
 
 /* Parameter gradient of a rollout from the history gcm_dense_rollout_fwd /
  * gcm_dense_rollout_persistent_fwd kept, when neither the observations nor the initial node matrix

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Micro-benchmark of cfg2's parameter backward: the record-walking kernel (gcm_dense_rows_bptt_cached:
-k_bptt_cached_graph) against the GEMM form (gcm_dense_rows_bptt_cached_hops: k_bptt_hops_graph, csrc/rows_bptt_hops.hip)
-on the SAME records.  The records of one cfg2 rollout (B = 256, N = T = 128, F = H = 32, TemporalBackedge([1, 2, 4]),
+k_bptt_cached_graph) against the GEMM form (csrc/rows_bptt_hops.hip) folded (gcm_dense_rows_bptt_cached_hops:
+k_bptt_hops_graph_fold) and unfolded (gcm_dense_rows_bptt_cached_hops_unfolded: k_bptt_hops_graph) on the SAME records.  The records of one cfg2 rollout (B = 256, N = T = 128, F = H = 32, TemporalBackedge([1, 2, 4]),
 tanh / tanh) are built through the C ABI with gcm_dense_rows_step_cached, as bench.py's time_step_kernel builds them
 for the cached step; then each entry - its gcm_sum_slabs_acc launch included - is timed with device events around
-KBENCH_ITERS back-to-back calls, the two entries alternating round by round in one process; median and minimum of
+KBENCH_ITERS back-to-back calls, the entries alternating round by round in one process; median and minimum of
 the rounds.  Prints one JSON object per entry and writes them to --out (default
 profiles/bptt_hops_kbench.jsonl).  Dev / reporting tool."""
 import argparse
@@ -66,7 +66,7 @@ gm = (ctypes.c_void_p * T)(*[g_mx[t].data_ptr() for t in range(T)])
 cur = (ctypes.c_uint8 * T)(*range(T))
 ws_bytes = max(lib.gcm_dense_rows_bptt_workspace_bytes(T, B, F, H1, H2), 4 * P * B)
 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-out = {k: torch.empty(P, device=dev) for k in ("walk", "hops")}
+out = {k: torch.empty(P, device=dev) for k in ("walk", "unfolded", "hops")}
 
 
 def walk():
@@ -82,6 +82,13 @@ def hops():
     assert rc == 0, rc
 
 
+def unfolded():
+    rc = lib.gcm_dense_rows_bptt_cached_hops_unfolded(sv, gm, T, H2, 1, p(params), 3, 1, 1, p(cX), p(cH), p(cA), cur,
+                                                      ctypes.addressof(desc), 1, T, None, p(out["unfolded"]), p(ws),
+                                                      ws_bytes, B, N, F, H1, H2, st)
+    assert rc == 0, rc
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -92,7 +99,7 @@ def timed(fn):
     return a.elapsed_time(b) * 1e3 / ITERS
 
 
-legs = {"walk": walk, "hops": hops}
+legs = {"walk": walk, "unfolded": unfolded, "hops": hops}
 for fn in legs.values():
     for _ in range(5):
         fn()
@@ -102,9 +109,10 @@ for _ in range(ROUNDS):
     for k, fn in legs.items():
         us[k].append(timed(fn))
 scale = float(out["walk"].abs().max())
-diff = float((out["walk"] - out["hops"]).abs().max())
 lines = []
-for k, entry in (("walk", "gcm_dense_rows_bptt_cached"), ("hops", "gcm_dense_rows_bptt_cached_hops")):
+for k, entry in (("walk", "gcm_dense_rows_bptt_cached"), ("unfolded", "gcm_dense_rows_bptt_cached_hops_unfolded"),
+                 ("hops", "gcm_dense_rows_bptt_cached_hops")):
+    diff = float((out["walk"] - out[k if k != "walk" else "hops"]).abs().max())
     lines.append({"bench": "bptt_hops_kbench", "entry": entry, "B": B, "N": N, "T": T, "F": F, "H1": H1, "H2": H2, "hops": HOPS,
                   "with": "gcm_sum_slabs_acc", "iters": ITERS, "rounds": ROUNDS,
                   "us_median": round(statistics.median(us[k]), 3), "us_min": round(min(us[k]), 3),

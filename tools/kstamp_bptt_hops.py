@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Phase breakdown of the GEMM-form cached backward (k_bptt_hops_graph, csrc/rows_bptt_hops.hip) on the records of one
+"""Phase breakdown of the GEMM-form cached backward (csrc/rows_bptt_hops.hip: k_bptt_hops_graph_fold, and with --form
+parent the kernel before the fold, k_bptt_hops_graph, behind gcm_dense_rows_bptt_cached_hops_unfolded) on the records of one
 cfg2 rollout (B = 256, N = T = 128, F = H = 32, TemporalBackedge([1, 2, 4]), tanh / tanh - built through the C ABI as
-tools/kbench_bptt_hops.py builds them) from in-kernel stamps of workgroup 0, wave 0 (diagnostic build:
+tools/kbench_bptt_hops.py builds them) from in-kernel stamps of workgroup 0, wave 0 - in the folded form a layer-2 wave - and, folded form, wave 4, a layer-1 wave (diagnostic build:
 make -C graph-conv-memory_amd/csrc stamps12).  Two libraries: the kernel as it ships with stamps at its phase edges,
 and one that also waits for every load before it computes (the round trip alone).  Stamps are s_memtime ticks, shown
 with each phase's share of the total.  Dev tool; --out appends the table as JSON lines."""
@@ -16,12 +17,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "graph-conv-memory_amd", "gcm", "_lib")
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
+ap.add_argument("--form", default="fold", choices=["fold", "parent"])
 ap.add_argument("--lib", default=None, help="(internal) one library per process: the stamps live in the library")
 args = ap.parse_args()
 
 if args.lib is None:   # one child per library (a process binds one libgcm_hip)
     for name in ("libgcm_hip_stamps12.so", "libgcm_hip_stamps12w.so"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--lib", os.path.join(LIBDIR, name)]
+        if args.form == "fold" and name.endswith("12w.so"):
+            continue   # (the waiting form is a mark of the unfolded kernel only)
+        cmd = [sys.executable, os.path.abspath(__file__), "--form", args.form, "--lib", os.path.join(LIBDIR, name)]
         if args.out:
             cmd += ["--out", args.out]
         rc = subprocess.run(cmd).returncode
@@ -74,6 +78,18 @@ ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 out = torch.empty(P, device=dev)
 lib.gcm_debug_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 
+FOLD_EDGES = [(0, 1, "layer-2 wave: stage, every load issued"),
+              (1, 2, "layer-2 wave: wait for the step loads; D2 -> LDS; barrier"),
+              (2, 3, "layer-2 wave: dW2 / db2 (32 MFMAs)"),
+              (3, 5, "layer-2 wave: partial slab -> LDS; barrier"),
+              (5, 6, "layer-2 wave: sum of four in wave order, slab stored"),
+              (16, 17, "layer-1 wave: stage, every load issued"),
+              (17, 18, "layer-1 wave: barrier (D2 of the layer-2 waves)"),
+              (18, 19, "layer-1 wave: A operands read from sD2 and summed"),
+              (19, 20, "layer-1 wave: tile product (32 MFMAs)"),
+              (20, 21, "layer-1 wave: G1, dW1 / db1 (32 MFMAs)"),
+              (21, 22, "layer-1 wave: partial slab -> LDS; barrier"),
+              (22, 23, "layer-1 wave: sum of four in wave order, slab stored")]
 EDGES = [(0, 1, "stage: every load issued"),
          (1, 2, "wait for the step loads; D2, dW2 / db2 (16 MFMAs), D2 -> LDS; barrier"),
          (2, 3, "U = D2 . [W_rel2 | W_root2] (16 MFMAs) -> LDS; barrier"),
@@ -82,14 +98,19 @@ EDGES = [(0, 1, "stage: every load issued"),
          (5, 6, "sum of eight in wave order, slab stored")]
 
 
+if args.form == "fold":
+    EDGES = FOLD_EDGES
+entry = lib.gcm_dense_rows_bptt_cached_hops if args.form == "fold" else lib.gcm_dense_rows_bptt_cached_hops_unfolded
+
+
 def run():
-    rc = lib.gcm_dense_rows_bptt_cached_hops(sv, gm, T, H2, 1, p(params), 3, 1, 1, p(cX), p(cH), p(cA), cur,
-                                             ctypes.addressof(desc), 1, T, None, p(out), p(ws), ws_bytes, B, N, F, H1, H2, st)
+    rc = entry(sv, gm, T, H2, 1, p(params), 3, 1, 1, p(cX), p(cH), p(cA), cur,
+               ctypes.addressof(desc), 1, T, None, p(out), p(ws), ws_bytes, B, N, F, H1, H2, st)
     assert rc == 0, rc
 
 
 lines = []
-for form in ("as shipped",):
+for form in (args.form,):
     R, acc, wait_acc = 20, [0.0] * len(EDGES), 0.0
     for it in range(R + 3):
         torch.cuda.synchronize()
@@ -109,8 +130,8 @@ for form in ("as shipped",):
     e1.record()
     torch.cuda.synchronize()
     us_pair = e0.elapsed_time(e1) / 50 * 1e3
-    total = sum(acc)
-    print("k_bptt_hops_graph, %s%s: workgroup 0, wave 0" % (form, " (waits for its loads before computing)" if waits else ""))
+    total = sum(a_ for a_, (e0_, _, _) in zip(acc, EDGES) if e0_ < 16)   # (wave 0's edges: begin to end)
+    print("k_bptt_hops_graph, %s%s: workgroup 0" % (form, " (waits for its loads before computing)" if waits else ""))
     for k, (a, b, name) in enumerate(EDGES):
         print("  %d -> %d  %-76s %8.1f ticks  %5.1f %%" % (a, b, name, acc[k], 100 * acc[k] / total))
     if waits:
