@@ -76,6 +76,21 @@ constexpr int RUN_ADJ_TAB = 256 + 128;   // FRESH: the adjacency pattern by colu
 #define GCM_RUN_FRESH_STORES_LATE 0
 #endif
 
+// Timing-only builds of the VALU form (their outputs are wrong; run under a kernel trace alone): 1 leaves its layer-2 loop
+// out, 2 both layer loops - what the layers cost in the eight-wave form (profiles/r14_bench_cfg2_cuts.jsonl).
+#ifndef GCM_RUN_CUT
+#define GCM_RUN_CUT 0
+#endif
+// ... and of the matrix-core form, a mask: 1 leaves the matrix instructions out, 2 the tanh, 4 the layers' global stores.
+#ifndef GCM_RUN_MFMA_CUT
+#define GCM_RUN_MFMA_CUT 0
+#endif
+// The matrix-core form's distance between LDS rows in floats (a multiple of 2, >= 32).  36 puts the 8-byte operand reads
+// of a tile's sixteen rows on distinct banks; with 32 they meet on eight and the launch took 19.3 us against 14.7 (the same file).
+#ifndef GCM_RUN_MFMA_RS
+#define GCM_RUN_MFMA_RS 36
+#endif
+
 // hops4: the distinct hops 0 < h < 128 ASCENDING, one byte each, 0xff in the unused slots.  nhs: N | H2 << 8 | self << 16.
 // Steps t < n <= RUN_CAP: row cur0 + t < N, observation tab.obs[t] [B, 32], record tab.rec[t] (o_*: CachedLayout;
 // rec = 0: mx alone).
@@ -92,16 +107,22 @@ constexpr int RUN_ADJ_TAB = 256 + 128;   // FRESH: the adjacency pattern by colu
 //     store per four columns, 1.0 at the sources (and at cur with self) and 0.0 elsewhere, read from a pattern table in
 //     LDS indexed by column - row - and rows [n, N) zero; workgroup 0 zeroes the paddings of the allocation.  Every
 //     address is stored once, so no order between waves is needed; phase D's scalar adjacency stores are left out.
-template <bool FRESH>
+//
+// MFMA: phases B and C on the fp32 matrix cores ("the layers on the matrix cores").  A wave owns the
+// sixteen steps 16 w ... 16 w + 15 and both column tiles of their 32 outputs; each of lean_half_chain's eight chains
+// (K half x parity x rel | root) is one accumulator of v_mfma_f32_16x16x4_f32, whose result is the k-ordered fmaf chain
+// from the accumulator: two instructions per chain, then the chain's own tree of adds.  The LDS rows are 36 floats
+// apart there, so that the 8-byte operand reads of sixteen rows fall on distinct banks.
+template <bool FRESH, bool MFMA>
 __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_run(
     const float* __restrict__ image, float* __restrict__ nodes, float* __restrict__ cH, const float* __restrict__ params,
     int cur0_arg, int n, unsigned hops4, unsigned nhs, float* __restrict__ adj, int64_t* __restrict__ count,
     float* __restrict__ cA, float* __restrict__ cX, uint32_t* __restrict__ flags, unsigned o_v, unsigned o_hdr,
     unsigned o_coef, unsigned o_live, int rec, RunTable tab, std::conditional_t<FRESH, FreshArgs, NoFresh> fr) {
-  constexpr int F = 32, H1 = 32, ROWS = 128 * 32;
+  constexpr int F = 32, H1 = 32, RS = MFMA ? GCM_RUN_MFMA_RS : 32, ROWS = 128 * RS;   // RS: floats from an LDS row to the next
   const int cur0 = FRESH ? 0 : cur0_arg;
   __shared__ __attribute__((aligned(16))) float sXH[2 * ROWS];            // x rows [128][32] | h1 rows [128][32]
-  __shared__ __attribute__((aligned(16))) float svw[RUN_WAVES * 128];     // each wave's lane exchange: two steps' vectors
+  __shared__ __attribute__((aligned(16))) float svw[MFMA ? 4 : RUN_WAVES * 128];   // each wave's lane exchange: two steps' vectors
   __shared__ __attribute__((aligned(16))) f32x2 sW[2 * 16 * 32 * 2];      // image3 as [layer][k][h][K half]: 16 KB
   __shared__ float sadj[FRESH ? RUN_ADJ_TAB : 1];
   const int lane = threadIdx.x & 63;
@@ -139,6 +160,21 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   f32x2 wst[RUN_WSTAGE];
   f32x4 wq[2];
   float bias1, bias2;
+  // MFMA: operand layout - lane (ar, ak) holds row ar of the wave's sixteen and k group ak; result layout - column
+  // ar + 16 ct, rows 4 ak + v.  The records of those rows and the biases of those columns
+  const int ar = lane & 15, ak = lane >> 4;
+  float* rec_a = nullptr;
+  float* rec_c[4] = {nullptr, nullptr, nullptr, nullptr};
+  float b1c[2] = {0.f, 0.f}, b2c[2] = {0.f, 0.f};
+  if constexpr (MFMA) {
+    const int ta = 16 * wv + ar;
+    rec_a = tab.rec[ta < n ? ta : n - 1];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int tc = 16 * wv + 4 * ak + v;
+      rec_c[v] = tab.rec[tc < n ? tc : n - 1];
+    }
+  }
   // FRESH: this workgroup's first elements of the image and of the packed vector (element gb + B * thread)
   float v_img = 0.f, v_pack = 0.f;
   const size_t e_first = (size_t)gb + (size_t)gridDim.x * threadIdx.x, e_wave = (size_t)gb + (size_t)gridDim.x * (64 * wv);
@@ -149,6 +185,14 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
     const float* b1 = params + 2 * H1 * F;
     bias1 = b1[fl];
     bias2 = b1[H1 + 2 * H2 * H1 + ol];
+    if constexpr (MFMA) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const int col = 16 * ct + ar;
+        b1c[ct] = b1[col];
+        b2c[ct] = b1[H1 + 2 * H2 * H1 + (col < H2 ? col : H2 - 1)];
+      }
+    }
   } else {
     // quad q = thread + 512 r of [m][h][k / 4]: columns 4 (q & 7) ... + 3 of row h of matrix m (zero past row H2)
 #pragma unroll
@@ -161,6 +205,14 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
     }
     bias1 = fr.hs.p[2][fl];
     bias2 = fr.hs.p[5][ol];
+    if constexpr (MFMA) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const int col = 16 * ct + ar;
+        b1c[ct] = fr.hs.p[2][col];
+        b2c[ct] = fr.hs.p[5][col < H2 ? col : H2 - 1];
+      }
+    }
     if (e_wave < (size_t)IMG_LAYOUT_FLOATS && e_first < (size_t)IMG_LAYOUT_FLOATS) {
       const int e = (int)e_first;
       v_img = head_image_value(fr.hs, e >> 12, (e >> 6) & 63, e & 63, F, H1, H2);
@@ -181,7 +233,7 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   {
     const int lo = cur0 - hmax > 0 ? cur0 - hmax : 0;
     const float* src = hs ? cH : nodes;
-    for (int r = lo + wv; r < cur0; r += RUN_WAVES) sXH[hs * ROWS + r * 32 + fl] = src[(g0 + (unsigned)r) * 32 + fl];
+    for (int r = lo + wv; r < cur0; r += RUN_WAVES) sXH[hs * ROWS + r * RS + fl] = src[(g0 + (unsigned)r) * 32 + fl];
   }
   if constexpr (!FRESH) {
 #pragma unroll
@@ -211,7 +263,7 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   for (int j = 0; j < RUN_PAIRS; ++j) {   // the observations: x rows in LDS, rows of the node matrix and of its cache
     const int t = 2 * (wv + RUN_WAVES * j) + hs;   // (rows cur and cur + 1 are 64 consecutive floats)
     if (t < n) {
-      sXH[(cur0 + t) * 32 + fl] = xo[j];
+      sXH[(cur0 + t) * RS + fl] = xo[j];
       const unsigned at = (g0 + (unsigned)(cur0 + t)) * F + fl;
       nodes[at] = xo[j];
       cX[at] = xo[j];
@@ -287,8 +339,116 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
   };
   // the layer's two products of one step in ONE lane: the two half-wave chains of lean_half_matvec, met in its order
   auto matvec = [&]() { return lean_half_chain(wa, sv, 0) + lean_half_chain(wb, sv, 1); };
+  // ---- the matrix-core form of a layer (MFMA) -------------------------------------------------------------------------
+  // This wave's steps are 16 w ... 16 w + 15.  In the operand layout lane (ar, ak) holds, of row ar, the columns
+  // f = 2 ak + 8 qf + p (qf < 4, p < 2) of the aggregate and of the row itself: the A operand of instruction i of the
+  // chain (K half kh, parity p) is column 16 kh + 2 (4 i + ak) + p, so qf = 2 kh + i, and the instruction's k index ak
+  // runs through the chain's j = 4 i ... 4 i + 3 in order.  The B operand is W[h = ar + 16 ct][that column], from the
+  // LDS image (one 16-byte read holds both K halves and both matrices).  A step past the run's end doubles the last.
+  const bool act = 16 * wv < n;   // (by wave)
+  const bool live_a = 16 * wv + ar < n;
+  const int cur_a = cur0 + (live_a ? 16 * wv + ar : n - 1);
+  int so[4];
+  bool sa[4];
+  {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) k += (int)(((hops4 >> (8 * i)) & 0xffu) <= (unsigned)cur_a);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {   // (sources() by row: slot q is row cur - hop[k - 1 - q], an empty slot adds 0.f)
+      const int idx = k - 1 - q;
+      sa[q] = idx >= 0;
+      so[q] = sa[q] ? RS * (cur_a - (int)((hops4 >> (8 * (idx & 3))) & 0xffu)) : 0;
+    }
+  }
+  auto operands = [&](const float* rows, f32x2 (&ag)[4], f32x2 (&own)[4]) {
+    const float* at = rows + 2 * ak;
+#pragma unroll
+    for (int qf = 0; qf < 4; ++qf) {
+      own[qf] = *reinterpret_cast<const f32x2*>(at + cur_a * RS + 8 * qf);
+      f32x2 v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x2 u = *reinterpret_cast<const f32x2*>(at + so[q] + 8 * qf);
+        v[q] = sa[q] ? u : f32x2{0.f, 0.f};
+      }
+      ag[qf] = (v[0] + v[1]) + (v[2] + v[3]);
+      ag[qf] = ag[qf] + (self ? own[qf] : f32x2{0.f, 0.f});
+    }
+  };
+  // the sixteen chains of the wave's tile, acc[ct][kh][p][rel | root], each from +0: instruction i = 0 of every chain,
+  // then i = 1 (no instruction waits for its own predecessor)
+  f32x4 acc[2][2][2][2];
+  auto products = [&](int layer, const f32x2 (&ag)[4], const f32x2 (&own)[4]) {
+    const float* sWf = reinterpret_cast<const float*>(sW);
+    f32x4 bw[2][2][2];   // [i][p][ct]: {K half 0 rel, root, K half 1 rel, root}
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+          bw[i][p][ct] = *reinterpret_cast<const f32x4*>(sWf + ((layer * 16 + 8 * i + 2 * ak + p) * 32 + 16 * ct + ar) * 4);
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) acc[ct][kh][p][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (GCM_RUN_MFMA_CUT & 1) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) acc[ct][0][0][0] = f32x4{ag[0][0] + bw[0][0][ct][0], own[1][1] + bw[1][1][ct][1], ag[2][0], own[3][1]};
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) {
+            const int qf = 2 * kh + i;
+            acc[ct][kh][p][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ag[qf][p], bw[i][p][ct][2 * kh], acc[ct][kh][p][0], 0, 0, 0);
+            acc[ct][kh][p][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(own[qf][p], bw[i][p][ct][2 * kh + 1], acc[ct][kh][p][1], 0, 0, 0);
+          }
+  };
+  // lean_half_chain's tree on the chains of result (ct, v): per K half (rel 0 + rel 1) + (root 0 + root 1), half 0 + half 1
+  auto tree = [&](int ct, int v) {
+    const float s0 = (acc[ct][0][0][0][v] + acc[ct][0][1][0][v]) + (acc[ct][0][0][1][v] + acc[ct][0][1][1][v]);
+    const float s1 = (acc[ct][1][0][0][v] + acc[ct][1][1][0][v]) + (acc[ct][1][0][1][v] + acc[ct][1][1][1][v]);
+    return s0 + s1;
+  };
+  auto run_tanh = [](float v) { return (GCM_RUN_MFMA_CUT & 2) ? v : gcm_tanh(v); };
+  constexpr bool STORES = !(GCM_RUN_MFMA_CUT & 4);
+  bool bad = false;
   // ---- phase B: layer 1 of this wave's steps (reads x rows, writes h1 rows) ------------------------------------------
-  weights(0);
+  if constexpr (MFMA) {
+    if (act) {
+      f32x2 ag[4], own[4];
+      operands(sXH, ag, own);
+      if (STORES && live_a) {
+        float* to = cA + (size_t)(g0 + (unsigned)cur_a) * F + 2 * ak;
+#pragma unroll
+        for (int qf = 0; qf < 4; ++qf) *reinterpret_cast<f32x2*>(to + 8 * qf) = ag[qf];
+      }
+      products(0, ag, own);
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int t = 16 * wv + 4 * ak + v;
+          const float h1c = run_tanh(b1c[ct] + tree(ct, v));
+          if (t < n) {
+            sXH[ROWS + (cur0 + t) * RS + 16 * ct + ar] = h1c;
+            if (STORES) cH[(size_t)(g0 + (unsigned)(cur0 + t)) * H1 + 16 * ct + ar] = h1c;
+          }
+        }
+    }
+  }
+  if constexpr (!MFMA) weights(0);
   auto layer1 = [&](int cur, bool live, const float (&xa)[4]) {
     const unsigned rc = g0 + (unsigned)cur;
     const float xc = sXH[cur * 32 + fl];
@@ -307,21 +467,46 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
       cH[rc * H1 + fl] = h1c;
     }
   };
+  if constexpr (!MFMA && GCM_RUN_CUT < 2) {   // (the VALU form)
 #pragma unroll
-  for (int j = 0; j < RUN_PAIRS; ++j) {
-    const int t0 = 2 * (wv + RUN_WAVES * j);
-    if (t0 >= n) break;
-    const bool live = t0 + hs < n;
-    const int cur = cur0 + (live ? t0 + hs : n - 1);
-    float xa[4];
-    if (cur0 + t0 < hmax) sources(cur, sXH, xa);
-    else sources_all(cur, sXH, xa);
-    layer1(cur, live, xa);
+    for (int j = 0; j < RUN_PAIRS; ++j) {
+      const int t0 = 2 * (wv + RUN_WAVES * j);
+      if (t0 >= n) break;
+      const bool live = t0 + hs < n;
+      const int cur = cur0 + (live ? t0 + hs : n - 1);
+      float xa[4];
+      if (cur0 + t0 < hmax) sources(cur, sXH, xa);
+      else sources_all(cur, sXH, xa);
+      layer1(cur, live, xa);
+    }
   }
   __syncthreads();
   // ---- phase C: layer 2 of this wave's steps (reads h1 rows) --------------------------------------------------------
-  weights(1);
-  bool bad = false;
+  if constexpr (MFMA) {
+    if (act) {
+      f32x2 ag[4], own[4];
+      operands(sXH + ROWS, ag, own);
+      if (STORES && rec && live_a) {   // the record's v section: (agg2 | h1) of the row
+        float* to = rec_a + o_v + gb * 2 * H1 + 2 * ak;
+#pragma unroll
+        for (int qf = 0; qf < 4; ++qf) {
+          *reinterpret_cast<f32x2*>(to + 8 * qf) = ag[qf];
+          *reinterpret_cast<f32x2*>(to + H1 + 8 * qf) = own[qf];
+        }
+      }
+      products(1, ag, own);
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const bool out = 16 * wv + 4 * ak + v < n && 16 * ct + ar < H2;
+          const float mx = run_tanh(b2c[ct] + tree(ct, v));
+          if (STORES && out) rec_c[v][gb * H2 + 16 * ct + ar] = mx;
+          bad = bad || (out && !isfinite(mx));
+        }
+    }
+  }
+  if constexpr (!MFMA) weights(1);
   auto layer2 = [&](int cur, bool live, float* saved, const float (&ha)[4]) {
     const float h1c = sXH[ROWS + cur * 32 + fl];
     asm volatile("" ::: "memory");
@@ -339,16 +524,18 @@ __global__ __launch_bounds__(64 * RUN_WAVES) void k_step_rows_cached_img4_lean_r
     }
     bad = bad || (live && fl < H2 && !isfinite(v));
   };
+  if constexpr (!MFMA && GCM_RUN_CUT < 1) {   // (the VALU form)
 #pragma unroll
-  for (int j = 0; j < RUN_PAIRS; ++j) {
-    const int t0 = 2 * (wv + RUN_WAVES * j);
-    if (t0 >= n) break;
-    const bool live = t0 + hs < n;
-    const int cur = cur0 + (live ? t0 + hs : n - 1);
-    float ha[4];
-    if (cur0 + t0 < hmax) sources(cur, sXH + ROWS, ha);
-    else sources_all(cur, sXH + ROWS, ha);
-    layer2(cur, live, recp[j], ha);
+    for (int j = 0; j < RUN_PAIRS; ++j) {
+      const int t0 = 2 * (wv + RUN_WAVES * j);
+      if (t0 >= n) break;
+      const bool live = t0 + hs < n;
+      const int cur = cur0 + (live ? t0 + hs : n - 1);
+      float ha[4];
+      if (cur0 + t0 < hmax) sources(cur, sXH + ROWS, ha);
+      else sources_all(cur, sXH + ROWS, ha);
+      layer2(cur, live, recp[j], ha);
+    }
   }
   // ---- phase D: what follows from cur and the hops alone, eight lanes per step (slot q = lane & 7) ------------------
   // With k = #{hop <= cur} of the ascending hops, the live list of row cur is cur - hop[k - 1 - q] for q < k and cur
@@ -426,6 +613,7 @@ struct Run {
   } head;
   bool absorb = true, fresh = false;
   FreshArgs fr{};
+  bool mfma = true;   // the node's layers run on the matrix cores (gcm_hip_run_mfma.h); false: the VALU form
 };
 
 // a graph call failed once: every later step of the process is a launch of its own
@@ -466,7 +654,8 @@ static void fill_args(Run& R, int n, RunArgs& a) {
                    R.fresh ? (void*)&R.fr : (void*)&a.none};
   for (int i = 0; i < 20; ++i) a.ptr[i] = ptr[i];
   a.p = hipKernelNodeParams{};
-  a.p.func = R.fresh ? (void*)k_step_rows_cached_img4_lean_run<true> : (void*)k_step_rows_cached_img4_lean_run<false>;
+  a.p.func = R.fresh ? (R.mfma ? (void*)k_step_rows_cached_img4_lean_run<true, true> : (void*)k_step_rows_cached_img4_lean_run<true, false>)
+                     : (R.mfma ? (void*)k_step_rows_cached_img4_lean_run<false, true> : (void*)k_step_rows_cached_img4_lean_run<false, false>);
   a.p.gridDim = dim3(R.B);
   a.p.blockDim = dim3(64 * RUN_WAVES);
   a.p.sharedMemBytes = 0;
@@ -809,6 +998,13 @@ extern "C" int gcm_rows_run_set_absorb(void* run, int on) {
 extern "C" int gcm_rows_run_absorbed(const void* run) {
   return run ? static_cast<const gcm_rows::Run*>(run)->stat_absorbed : 0;
 }
+// (the form is read whenever the node's parameters are made: set it before the capture, not inside a run)
+extern "C" int gcm_rows_run_set_mfma(void* run, int on) {
+  GCM_REQUIRE(run);
+  static_cast<gcm_rows::Run*>(run)->mfma = on != 0;
+  return GCM_OK;
+}
+extern "C" int gcm_rows_run_mfma(const void* run) { return run && static_cast<const gcm_rows::Run*>(run)->mfma ? 1 : 0; }
 extern "C" int gcm_rows_run_absorb_enabled(void) { return gcm_rows::g_absorb_ok.load() ? 1 : 0; }
 
 extern "C" int gcm_dense_rows_head_fused_run(void* run, const float* const* srcs_host, const size_t* lens_host, int n,

@@ -58,6 +58,7 @@ struct StepCfg {
   bool merge_captured = true;   // lean cached steps captured back to back become one graph node (A/B switch)
   int merge_cap = 0;            // steps per such node (tests split a run with it); 0: the library's cap
   bool absorb_head = true;      // ... and the rollout's head launch in front of step 0 is absorbed into it (A/B switch)
+  bool run_mfma = true;         // ... and that node runs its layers on the fp32 matrix cores (A/B switch: the VALU form)
   int64_t P;
   bool has_distance = false;
   at::Tensor ws;   // scratch of the distance selectors
@@ -711,7 +712,7 @@ struct RowsFast {
   // the chain's run object (gcm_hip_run.h): inside a stream capture, cached lean steps that follow one another directly
   // are appended to ONE graph node.  Reset whenever the chain is re-armed or a step comes through the checked entry.
   void* mrun = nullptr;
-  int mrun_cap = 0, mrun_absorb = -1;
+  int mrun_cap = 0, mrun_absorb = -1, mrun_mfma = -1;
 
   RowsFast(const std::vector<std::pair<pybind11::object, pybind11::object>>& specs,
            const std::vector<pybind11::object>& hooks)
@@ -740,6 +741,10 @@ struct RowsFast {
       mrun_cap = cap;
     }
     set_absorb(cfg->absorb_head);
+    if (mrun && (int)cfg->run_mfma != mrun_mfma) {
+      gcm_rows_run_set_mfma(mrun, cfg->run_mfma ? 1 : 0);
+      mrun_mfma = (int)cfg->run_mfma;
+    }
     return mrun;
   }
   void set_absorb(bool on) {
@@ -764,6 +769,7 @@ struct RowsFast {
     if (mrun && !last_cached_eager) gcm_rows_run_stats(mrun, out);
     return {out[0], out[1]};
   }
+  bool run_mfma() const { return mrun ? gcm_rows_run_mfma(mrun) != 0 : (cfg ? cfg->run_mfma : true); }
   int head_absorbed() const { return mrun && !last_cached_eager ? gcm_rows_run_absorbed(mrun) : 0; }
 
   bool hooks_registered() const {   // torch.nn.Module.__call__ has work to do: take the long way
@@ -2931,6 +2937,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_col_cache", [](StepCfg& c, bool on) { c.col_cache = on; })
       .def("set_merge_captured", [](StepCfg& c, bool on, int cap) { c.merge_captured = on; c.merge_cap = cap; })
       .def("set_absorb_head", [](StepCfg& c, bool on) { c.absorb_head = on; })
+      .def("set_run_mfma", [](StepCfg& c, bool on) { c.run_mfma = on; })
       .def("cached_launches", [](StepCfg& c, int B) {   // launches per cached step (0: no cached form)
         return gcm_dense_rows_cached_launches(c.descs.empty() ? nullptr : c.descs.data(), (int)c.descs.size(),
                                               c.has_bias | c.cached_flags, B, c.N, c.F, c.H1, c.H2);
@@ -2953,6 +2960,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("col_steps", [](RowsFast& f) { return f.col_steps; })
       .def("merge_stats", &RowsFast::merge_stats)
       .def("head_absorbed", &RowsFast::head_absorbed)
+      .def("run_mfma", &RowsFast::run_mfma)
       .def("has_chain", [](RowsFast& f) { return f.node != nullptr || f.dxc != nullptr; });
   pybind11::class_<LearnedCfg>(m, "LearnedCfg")
       .def(pybind11::init<int, int, int, int, int, int, int, double, double, double>())

@@ -76,6 +76,8 @@ HEAD_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_head.h"))
 RUN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_run.h"))
 # and the section from gcm_hip_run_head.h (the rollout's head launch absorbed into that node)
 RUN_HEAD_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_run_head.h"))
+# and the section from gcm_hip_run_mfma.h (that node's layers on the fp32 matrix cores, and the switch back)
+RUN_MFMA_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_run_mfma.h"))
 # and the section from gcm_hip_knn.h (KNNEdge: the distance modes that carry k)
 _KNN_HEADER = _abi.header("gcm_hip_knn.h")
 KNN_PROTOTYPES = _abi.prototypes(_KNN_HEADER)
@@ -137,6 +139,7 @@ def lib():
         bind(handle, KNN_PROTOTYPES)
         bind(handle, RUN_PROTOTYPES)
         bind(handle, RUN_HEAD_PROTOTYPES)
+        bind(handle, RUN_MFMA_PROTOTYPES)
         got, want = handle.gcm_abi_version(), _CONSTANTS["GCM_ABI_VERSION"]
         if got != want:     # a library older than the header the prototypes were read from
             raise HipLibraryError(f"{_LIB_PATH} has ABI revision {got}, include/gcm_hip.h is at {want}: "

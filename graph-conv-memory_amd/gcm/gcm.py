@@ -317,6 +317,11 @@ class DenseGCM(torch.nn.Module):
         # node is destroyed ("the head absorbed"): one dependent launch less per replay.  False (env
         # GCM_ABSORB_HEAD=0): the head stays a node (A/B); the same bits either way.  Read when a chain is armed
         self.rows_absorb_head = os.environ.get("GCM_ABSORB_HEAD", "1") == "1"
+        # True: the merged node runs the two layers of its steps on the fp32 matrix cores - one accumulator of
+        # v_mfma_f32_16x16x4_f32 per chain of the per-step kernel's product, a wave per sixteen steps ("the
+        # layers on the matrix cores").  False (env GCM_RUN_MFMA=0): the VALU form of the same kernel (A/B); the same
+        # bits either way.  Read when a chain is armed
+        self.rows_run_mfma = os.environ.get("GCM_RUN_MFMA", "1") == "1"
         self._head_ready = None   # (cfg, grad mode) of the packed vector forward(x, None) has just built with the state
         # False: rollout() from empty graphs with forward temporal hops runs the persistent per-graph kernel of round 1
         # instead of the two-launch time-parallel forward (csrc/rollout_tp.hip) - A/B tests
@@ -368,20 +373,25 @@ class DenseGCM(torch.nn.Module):
                 n += cfg._rows_fast.steps()
         return n
 
-    def merge_stats(self, head=False):
+    def merge_stats(self, head=False, form=False):
         """What became of this module's cached steps in the stream capture seen last: {"nodes": graph nodes they were
         launched as, "merged_steps": steps appended to an existing node instead (rows_merge_captured)}.  Both 0 after
         an eager step.  head=True: also "head_absorbed", the head launches of forward(x, None) whose node a merged node
-        took the place of (rows_absorb_head)."""
+        took the place of (rows_absorb_head).  form=True: also "run_mfma", whether the merged nodes run their layers on
+        the matrix cores (rows_run_mfma, as the chains armed last took it)."""
         nodes = merged = absorbed = 0
+        mfma = bool(self.rows_run_mfma)
         for cfg in self._cfg_cache.values():
             if cfg is not False and cfg._rows_fast is not None:
                 a, b = cfg._rows_fast.merge_stats()
                 nodes, merged = nodes + a, merged + b
                 absorbed += cfg._rows_fast.head_absorbed()
+                mfma = mfma and bool(cfg._rows_fast.run_mfma())
         out = {"nodes": nodes, "merged_steps": merged}
         if head:
             out["head_absorbed"] = absorbed
+        if form:
+            out["run_mfma"] = mfma
         return out
 
     def learned_fast_steps(self):
@@ -898,6 +908,7 @@ class DenseGCM(torch.nn.Module):
                 cfg._cpp.set_hops_fold(bool(self.rows_hops_fold))
                 cfg._cpp.set_merge_captured(bool(self.rows_merge_captured), int(self.rows_merge_cap or 0))
                 cfg._cpp.set_absorb_head(bool(self.rows_absorb_head))
+                cfg._cpp.set_run_mfma(bool(self.rows_run_mfma))
             image = self._packed_cache[5]
             if image is not None and self._packed_cache[1] is root:
                 fast.set_head_image(root, image)   # (the first cached step takes it iff it is armed with this vector)

@@ -836,6 +836,9 @@ int gcm_dense_rows_step_cached_ws(const float* obs, float* nodes, float* adj, in
 /* ... and the rollout's head launch absorbed into that node (gcm_dense_rows_head_fused with the run object in front).
  * Declared in gcm_hip_run_head.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_run_head.h"
+/* ... and the form of that node's two layers (fp32 matrix cores, or the VALU form as an A/B switch).
+ * Declared in gcm_hip_run_mfma.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_run_mfma.h"
 /* EuclideanEdge (distance.py:41-49, not bidirectional) as the ONLY selector of such a chain: the distance kernel and
  * the cached step as one launch (the step is the tail of the matrix-core distance kernel's first wave) -
  * gcm_dense_rows_step_cached_ws takes this path by itself when the shapes allow (>= 32 current rows, F in {32, 64},

@@ -8,7 +8,8 @@
 One JSON line per form: us per replay, us per step, and merge_stats() where the module has it (so the same file runs
 on a tree from before the switch).  --label names the leg; GCM_MERGE_CAPTURED=0 is the switch-off leg, and
 GCM_ABSORB_HEAD=0 the leg that merges the steps but keeps the rollout's head launch a node of its own (merge_stats
-then reports head_absorbed: 0).  Dev tool."""
+then reports head_absorbed: 0), and GCM_RUN_MFMA=0 the leg whose merged node runs its layers in the VALU form instead of
+on the matrix cores (merge_stats then reports run_mfma: false).  Dev tool."""
 import argparse
 import json
 import os
@@ -48,7 +49,10 @@ def measure(form, dev, replays, repeats):
         loop()
     stats = None
     if hasattr(mem, "merge_stats"):   # (head=True: trees that can absorb the head launch say whether they did)
-        stats = mem.merge_stats(head=True) if hasattr(mem, "rows_absorb_head") else mem.merge_stats()
+        if hasattr(mem, "rows_run_mfma"):   # (and which form the merged node's layers run in)
+            stats = mem.merge_stats(head=True, form=True)
+        else:
+            stats = mem.merge_stats(head=True) if hasattr(mem, "rows_absorb_head") else mem.merge_stats()
     for _ in range(20):
         graph.replay()
     torch.cuda.synchronize()
