@@ -165,6 +165,20 @@ def stream():
     return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
+def kernel_ready(t):
+    """t as a kernel may read it: contiguous and with a 16-byte aligned data pointer (the kernels use 16-byte vector
+    accesses).  A tensor that already is both comes back as the same object; any other - a strided or expanded view, a
+    contiguous view that starts at an odd element of its storage - is copied into an allocation of its own, under
+    autograd, so a gradient finds its way back to the view's base."""
+    if t is None:
+        return None
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def on_device(*tensors):
     """Validate that every given tensor lives on a HIP device and is contiguous."""
     for t in tensors:

@@ -213,7 +213,7 @@ class _DenseGraphConv(torch.autograd.Function):
         Fo = w_rel.shape[0]
         need_x, need_adj, need_wrel, need_b, need_wroot, _ = ctx.needs_input_grad
         need_b = need_b and ctx.has_bias
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         lib = _hip.lib()
         g_x = torch.empty_like(x) if need_x else None
@@ -837,7 +837,7 @@ class _CsrGraphConv(torch.autograd.Function):
         need_x, need_we, need_wrel, need_b, need_wroot, _, _ = ctx.needs_input_grad
         need_b = need_b and ctx.has_bias
         need_we = need_we and w_edge is not None
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         lib = _hip.lib()
         E = graph.E
@@ -894,7 +894,7 @@ class _DenseGCNConv(torch.autograd.Function):
         Fo = w.shape[0]
         need_x, need_adj, need_w, need_b, _, _ = ctx.needs_input_grad
         need_b = need_b and ctx.has_bias
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         lib = _hip.lib()
         g_x = torch.empty_like(x) if need_x else None
@@ -947,7 +947,7 @@ class _CsrGCNConv(torch.autograd.Function):
         need_x, need_we, need_w, need_b, _, _, _, _ = ctx.needs_input_grad
         need_b = need_b and ctx.has_bias
         need_we = need_we and w_edge is not None
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         lib = _hip.lib()
         col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_we) and E > 0)
@@ -993,7 +993,7 @@ class _DenseGINAggregate(torch.autograd.Function):
         x, adj, eps = ctx.saved_tensors
         B, N, F = x.shape
         need_x, need_adj, need_eps, _ = ctx.needs_input_grad
-        g_h = g_h.contiguous()
+        g_h = _hip.kernel_ready(g_h)
         dev = x.device
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
@@ -1032,7 +1032,7 @@ class _CsrGINAggregate(torch.autograd.Function):
         M, F = x.shape
         E = graph.E
         need_x, need_eps, _ = ctx.needs_input_grad
-        g_h = g_h.contiguous()
+        g_h = _hip.kernel_ready(g_h)
         dev = x.device
         col_ptr, rows, _ = _csc_or_none(graph, need_x and E > 0)
         g_x = torch.empty_like(x) if need_x else None
@@ -1084,7 +1084,7 @@ class _DenseGATConv(torch.autograd.Function):
         H, C, concat, slope, has_bias = ctx.cfg
         B, N, Fi = x.shape
         need_x, _, need_w, need_as, need_ad, need_b = ctx.needs_input_grad[:6]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         lib = _hip.lib()
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w) if need_w else None
@@ -1139,7 +1139,7 @@ class _CsrGATConv(torch.autograd.Function):
         M, Fi = x.shape
         E = graph.E
         need_x, need_w, need_as, need_ad, need_b = ctx.needs_input_grad[:5]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         lib = _hip.lib()
         col_ptr, rows, perm = _csc_or_none(graph, E > 0 and (need_x or need_w or need_as or need_ad))
         g_x = torch.empty_like(x) if need_x else None
@@ -1201,7 +1201,7 @@ class _DenseTransformerConv(torch.autograd.Function):
     def backward(ctx, g_out):
         x, w_all, w_beta, saved = ctx.saved_tensors
         need_x, _, need_w, need_b, need_beta = ctx.needs_input_grad[:5]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w_all) if need_w else None
         g_b = torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need_b else None
@@ -1243,7 +1243,7 @@ class _CsrTransformerConv(torch.autograd.Function):
         x, w_all, w_beta, saved = ctx.saved_tensors
         graph = ctx.graph
         need_x, need_w, need_b, need_beta = ctx.needs_input_grad[:4]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         col_ptr, rows, perm = _csc_or_none(graph, graph.E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w_all) if need_w else None
@@ -1298,7 +1298,7 @@ class _DenseResGatedConv(torch.autograd.Function):
     def backward(ctx, g_out):
         x, adj, w_all, saved = ctx.saved_tensors
         need_x, need_adj, need_w, need_b, need_bias = ctx.needs_input_grad[:5]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         C = ctx.dims[3]
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
@@ -1341,7 +1341,7 @@ class _CsrResGatedConv(torch.autograd.Function):
         x, w_all, saved = ctx.saved_tensors
         graph = ctx.graph
         need_x, need_w, need_b, need_bias = ctx.needs_input_grad[:4]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         col_ptr, rows, _ = _csc_or_none(graph, graph.E > 0)
         g_x = torch.empty_like(x) if need_x else None
         g_w = torch.empty_like(w_all) if need_w else None
@@ -1410,7 +1410,7 @@ class _DenseGatedGraphConv(torch.autograd.Function):
         adj, weight, w_ih, w_hh, saved = ctx.saved_tensors
         B, N, Fi, C, L = ctx.dims
         need_x, need_adj = ctx.needs_input_grad[:2]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         g_x = torch.empty(B, N, Fi, device=adj.device, dtype=_f32) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
         g_weight, g_w_ih, g_w_hh, g_b_ih, g_b_hh = _gated_grads(ctx, weight, w_ih, 2)
@@ -1454,7 +1454,7 @@ class _CsrGatedGraphConv(torch.autograd.Function):
         M, E, Fi, C, L = ctx.dims
         need_x, need_we = ctx.needs_input_grad[:2]
         need_we = need_we and w_edge is not None
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         col_ptr, rows, perm = _csc_or_none(graph, E > 0)
         g_x = torch.empty(M, Fi, device=g_out.device, dtype=_f32) if need_x else None
         g_we = torch.zeros_like(w_edge) if need_we else None
@@ -1502,7 +1502,7 @@ class _DenseTagConv(torch.autograd.Function):
         B, N, Fi, Fo, K = ctx.dims
         need_x, need_adj, need_w, need_b = ctx.needs_input_grad[:4]
         need_b = need_b and ctx.has_bias
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
         g_w = torch.empty_like(weight) if need_w else None
@@ -1553,7 +1553,7 @@ class _CsrTagConv(torch.autograd.Function):
         need_x, need_we, need_w, need_b = ctx.needs_input_grad[:4]
         need_b = need_b and ctx.has_bias
         need_we = need_we and ctx.has_w
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_we) and E > 0)
         g_x = torch.empty_like(x) if need_x else None
@@ -1616,7 +1616,7 @@ class _DenseAggrConv(torch.autograd.Function):
         need_b = need_b and ctx.has_bias
         need_wroot = need_wroot and w_root is not None
         need_adj = need_adj and ctx.aggr == _hip.AGGR_MEAN
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
@@ -1673,7 +1673,7 @@ class _CsrAggrConv(torch.autograd.Function):
         need_b = need_b and ctx.has_bias
         need_wroot = need_wroot and w_root is not None
         need_we = need_we and w_edge is not None
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         wanted = (need_x or need_we) and E > 0
         col_ptr, rows, perm = _csc_or_none(graph, wanted)
@@ -1775,7 +1775,7 @@ class _DensePNAConv(torch.autograd.Function):
         x, adj, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, ab, cat, h, cnt, stat, winner = ctx.saved_tensors
         cfg = ctx.cfg
         B, N, _ = x.shape
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         grads = _pna_grads(ctx, (x, w_pre, b_pre, w_post, b_post, w_lin, b_lin))
         ws, ws_bytes = _scratch("gcm_dense_pnaconv_bwd", B, N, *cfg.dims(), cfg.A, cfg.S, device=x.device)
         _call("gcm_dense_pnaconv_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_pre), _hip.ptr(w_post),
@@ -1816,7 +1816,7 @@ class _CsrPNAConv(torch.autograd.Function):
         x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, avg_deg, ab, cat, h, cnt, stat, winner = ctx.saved_tensors
         cfg, graph = ctx.cfg, ctx.graph
         M, E = graph.M, graph.E
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         grads = _pna_grads(ctx, (x, w_pre, b_pre, w_post, b_post, w_lin, b_lin))
         col_ptr, rows, perm = _csc_or_none(graph, E > 0 and any(g is not None for g in grads[:3]))
         ws, ws_bytes = _scratch("gcm_csr_pnaconv_bwd", M, E, *cfg.dims(), cfg.A, cfg.S, device=x.device)
@@ -1884,7 +1884,7 @@ class _DenseRGCNConv(torch.autograd.Function):
         need_x, need_adj, _, need_w, need_root, need_b, _ = ctx.needs_input_grad
         need_root = need_root and root is not None
         need_b = need_b and ctx.has_bias
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         g_x = torch.empty_like(x) if need_x else None
         g_adj = torch.empty_like(adj) if need_adj else None
@@ -1937,7 +1937,7 @@ class _CsrRGCNConv(torch.autograd.Function):
         need_x, _, need_w, need_root, need_b, _, _, _ = ctx.needs_input_grad
         need_root = need_root and root is not None
         need_b = need_b and ctx.has_bias
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         dev = x.device
         col_ptr, rows, perm = _csc_or_none(graph, (need_x or need_w) and E > 0)
         g_x = torch.empty_like(x) if need_x else None
@@ -2011,7 +2011,7 @@ class _DenseGENAgg(torch.autograd.Function):
         xs, bits, t, agg, lse = ctx.saved_tensors
         B, N, C = xs.shape
         need_x, _, need_t, _ = ctx.needs_input_grad
-        g_agg = g_agg.contiguous()
+        g_agg = _hip.kernel_ready(g_agg)
         g_xs = torch.empty_like(xs) if need_x else None
         g_t = torch.empty_like(t) if need_t else None
         ws, ws_bytes = _scratch("gcm_dense_gen_bwd", B, N, C, device=xs.device) if need_t else (None, 0)
@@ -2047,7 +2047,7 @@ class _CsrGENAgg(torch.autograd.Function):
         M, C = xs.shape
         E = graph.E
         need_x, need_t, _, _ = ctx.needs_input_grad
-        g_agg = g_agg.contiguous()
+        g_agg = _hip.kernel_ready(g_agg)
         col_ptr, rows, _ = _csc_or_none(graph, need_x and E > 0)
         g_xs = torch.empty_like(xs) if need_x else None
         g_t = torch.empty_like(t) if need_t else None
@@ -2109,7 +2109,7 @@ class _DenseEdgeMax(torch.autograd.Function):
         P, Q, w2, winner = ctx.saved_tensors
         B, N, H = P.shape
         C = w2.shape[0]
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         g_P, g_Q, g_w2, g_b2 = _edgemax_grads(ctx, (0, 1, 3, 4), P, w2, ctx.b2_shape)
         ws, ws_bytes = (_scratch("gcm_dense_edgemax_bwd", B, N, H, C, device=P.device)
                         if g_w2 is not None or g_b2 is not None else (None, 0))
@@ -2148,7 +2148,7 @@ class _CsrEdgeMax(torch.autograd.Function):
         graph = ctx.graph
         M, H = P.shape
         C, E = w2.shape[0], graph.E
-        g_out = g_out.contiguous()
+        g_out = _hip.kernel_ready(g_out)
         g_P, g_Q, g_w2, g_b2 = _edgemax_grads(ctx, (0, 1, 2, 3), P, w2, ctx.b2_shape)
         col_ptr, rows, perm = _csc_or_none(graph, g_Q is not None and E > 0)
         ws, ws_bytes = (_scratch("gcm_csr_edgemax_bwd", M, E, H, C, device=P.device)

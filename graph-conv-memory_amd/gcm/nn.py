@@ -4,6 +4,8 @@ tests/test_sparse_gcm.py:310-323).  Parameter names/layout follow modern PyG
 (`lin_rel.{weight,bias}`, `lin_root.weight`) so state_dicts interchange between
 the dense and sparse layers (tests/test_sparse_gcm.py:326-330).
 """
+import itertools
+
 import torch
 
 from . import _hip, _ops
@@ -31,18 +33,150 @@ class SkinnyLinear(torch.nn.Linear):
 _AGGRS = ("add", "mean", "max")
 
 
-def _dense_inputs(x, adj):
-    x = x.unsqueeze(0) if x.dim() == 2 else x
-    adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
-    if adj.dtype != torch.float32:
-        raise TypeError("adj must be float32 (gcm.py:203); got %s" % adj.dtype)
-    if adj.shape[0] != x.shape[0]:
-        adj = adj.expand(x.shape[0], -1, -1)
-    return x, adj
+_F32, _I64 = (torch.float32,), (torch.int64,)
+_MASK_DTYPES = (torch.bool, torch.float32)
+_CODE_DTYPES = (torch.float32, torch.int64)      # RGCN's relation codes
+
+
+def _state(conv):
+    """[(name, tensor)] over the parameters and buffers of a layer (walked once per call)."""
+    return list(itertools.chain(conv.named_parameters(), conv.named_buffers()))
+
+
+def _check_dtypes(layer, state, operands):
+    """Step 1 of the calling contract.  operands: (name, tensor | None, accepted dtypes).  Nothing is cast: a float64
+    pipeline would lose its precision without a word, and a narrower type would be read past its end."""
+    for name, t, dtypes in operands:
+        if t is not None and t.dtype not in dtypes:
+            want = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+            raise TypeError(f"{layer}: {name} must be {want}; got {t.dtype}")
+    for name, p in state:
+        if p.is_floating_point() and p.dtype != torch.float32:
+            raise TypeError(f"{layer}: parameter {name} must be float32; got {p.dtype} (the kernels are float32: "
+                            "module.double() / .half() are not supported)")
+
+
+def _check_devices(layer, state, operands):
+    """Step 3 of the calling contract: every operand, then every parameter and buffer, on the current HIP device."""
+    tensors = [(name, t) for name, t, _ in operands if t is not None]
+    tensors += [("parameter " + name, p) for name, p in state]
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise _hip.HipLibraryError(f"{layer}: {name} is on '{t.device}': gcm (MI355X build) runs on HIP devices "
+                                       "only. There is no CPU fallback.")
+    cur = torch.cuda.current_device()
+    for name, t in tensors:
+        if t.device.index != cur:
+            raise _hip.HipLibraryError(f"{layer}: {name} is on {t.device} but the current device is cuda:{cur}: the "
+                                       "kernels launch on the current device's stream - wrap the call in "
+                                       "torch.cuda.device(...)")
+
+
+def _check_width(layer, F, in_channels, max_channels, width_error):
+    """x of F features beside the layer's in_channels (`width_error(F)`: a layer's own wording of the mismatch), or
+    beside GatedGraphConv's rule, in PyG's words: any width up to out_channels."""
+    if in_channels is not None and F != in_channels:
+        raise ValueError(f"{layer}: " + (width_error(F) if width_error else
+                                         f"x has {F} features, the layer has in_channels={in_channels}"))
+    if max_channels is not None and F > max_channels:
+        raise ValueError(f"{layer}: The number of input channels is not allowed to be larger than the number of "
+                         "output channels")
+
+
+def _dense_contract(conv, x, adj, mask=None, in_channels=None, planes=(), device=True, width_error=None,
+                    max_channels=None):
+    """The calling contract of the dense layers, checked before anything else runs -> (x [B,N,F], adj [B,N,N], *planes
+    [B,N,N]) as the kernels read them.  In this order, so that the first two fail alike on a machine without a GPU:
+    1. dtype (TypeError): x, adj and every floating parameter and buffer float32, mask bool or float32, `planes`
+       ((name, tensor) pairs of adj's shape: RGCN's relation codes) float32 or int64.  Nothing is cast.
+    2. shape (ValueError): x [B,N,F] or [N,F], F == in_channels or F <= max_channels when one is given; adj and the
+       planes [B,N,N], [1,N,N] or [N,N]; mask with B * N elements.
+    3. device (_hip.HipLibraryError): every operand and every parameter and buffer on the current HIP device.
+    4. layout: any strides go, zero strides of an expand included.  What comes back is contiguous and 16-byte aligned
+       (_hip.kernel_ready): a copy where the operand was not, the operand itself where it was; a broadcast adjacency is
+       materialised per batch entry.  The copies are made under autograd.  The mask is not copied (_masked reshapes it).
+    Not checked: the alignment of the parameters (a misaligned view assigned as a module's parameter is handed to the
+    kernels as it is).  `device=False` skips step 3 alone (the CPU tests of steps 1, 2 and 4)."""
+    layer = type(conv).__name__
+    planes = list(planes)
+    operands = [("x", x, _F32), ("adj", adj, _F32), ("mask", mask, _MASK_DTYPES)]
+    operands += [(name, t, _CODE_DTYPES) for name, t in planes]
+    state = _state(conv)
+    _check_dtypes(layer, state, operands)
+    xs = tuple(x.shape)
+    if len(xs) not in (2, 3):
+        raise ValueError(f"{layer}: x must be [B,N,F] or [N,F]; got {list(xs)}")
+    _check_width(layer, xs[-1], in_channels, max_channels, width_error)
+    B, N = (1, xs[0]) if len(xs) == 2 else xs[:2]
+    for name, t in [("adj", adj)] + planes:
+        s = tuple(t.shape)
+        if len(s) not in (2, 3) or s[-2:] != (N, N) or (len(s) == 3 and s[0] not in (1, B)):
+            raise ValueError(f"{layer}: {name} must be [{B},{N},{N}], [1,{N},{N}] or [{N},{N}] beside x {list(xs)}; "
+                             f"got {list(s)}")
+    if mask is not None and mask.numel() != B * N:
+        raise ValueError(f"{layer}: mask must hold B * N = {B * N} entries; got {list(mask.shape)}")
+    if device:
+        _check_devices(layer, state, operands)
+    out = [_hip.kernel_ready(x.unsqueeze(0) if len(xs) == 2 else x)]
+    for _, t in [("adj", adj)] + planes:
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        out.append(_hip.kernel_ready(t.expand(B, -1, -1) if t.shape[0] != B else t))
+    return out
+
+
+def _sparse_contract(conv, x, edge_index, in_channels=None, edge_weight=None, edge_attr=None, edge_type=None,
+                     type_dtypes=_I64, device=True, width_error=None, weight_per_edge=False, max_channels=None):
+    """The calling contract of the sparse layers, checked before anything else runs -> (x [M,F], edge_index [2,E],
+    edge_weight, edge_type) as the kernels and the indexing read them.  Steps and order as _dense_contract:
+    1. dtype (TypeError): x, edge_weight, edge_attr and every floating parameter and buffer float32; edge_index
+       int64, as in PyG; edge_type one of `type_dtypes`.  Nothing is cast.
+    2. shape (ValueError): x [M,F], F == in_channels or F <= max_channels when one is given; edge_index [2,E].  The
+       length of edge_weight / edge_type stays each layer's own rule: GraphConv and its relatives ignore a weight
+       vector of another length, GCNConv (`weight_per_edge`) refuses it here.
+    3. device (_hip.HipLibraryError): every operand and every parameter and buffer on the current HIP device.
+    4. layout: any strides go (`pairs.t()` of an [E,2] list, a slice of a wider buffer).  What comes back is
+       contiguous and 16-byte aligned (_hip.kernel_ready): a copy where the operand was not, the operand itself where
+       it was.  An edge_index that carries a `gcm_graph` for these M nodes comes back as it is: the index is the
+       library's own and the list is not read again.  edge_attr is ignored by every layer here and is not copied.
+    Not checked: node ids in edge_index outside [0, M) (finding them takes a pass over the list and a device
+    synchronisation), and the alignment of the parameters.  `device=False` skips step 3 alone."""
+    layer = type(conv).__name__
+    operands = [("x", x, _F32), ("edge_index", edge_index, _I64), ("edge_weight", edge_weight, _F32),
+                ("edge_attr", edge_attr, _F32), ("edge_type", edge_type, type_dtypes)]
+    state = _state(conv)
+    _check_dtypes(layer, state, operands)
+    xs, es = tuple(x.shape), tuple(edge_index.shape)
+    if len(xs) != 2:
+        raise ValueError(f"{layer}: x must be [M,F]; got {list(xs)}")
+    _check_width(layer, xs[1], in_channels, max_channels, width_error)
+    if len(es) != 2 or es[0] != 2:
+        raise ValueError(f"{layer}: edge_index must be [2,E] = (source, sink); got {list(es)}")
+    if weight_per_edge and edge_weight is not None and edge_weight.numel() != es[1]:
+        raise ValueError(f"{layer}: edge_weight has {edge_weight.numel()} entries for {es[1]} edges")
+    if device:
+        _check_devices(layer, state, operands)
+    graph = getattr(edge_index, "gcm_graph", None)
+    if graph is None or graph.M != xs[0]:
+        edge_index = _hip.kernel_ready(edge_index)
+    w = _hip.kernel_ready(edge_weight)
+    if w is not edge_weight and getattr(edge_weight, "gcm_unit_weights", False):
+        w.gcm_unit_weights = True
+    return _hip.kernel_ready(x), edge_index, w, _hip.kernel_ready(edge_type)
+
+
+def _ready_grad(out):
+    """Behind the torch modules that end a layer (GINConv's nn, GENConv's mlp, PNAConv's deeper post layers): the
+    output's gradient reaches their backward contiguous and aligned too, as the conv Functions make it in theirs
+    (_hip.kernel_ready; a contiguous one passes untouched).  Without it a transposed or zero-stride grad_output - the
+    latter is what out.sum().backward() produces - takes another path through torch's GEMMs, and the layer's gradients
+    would depend on how its caller laid grad_output out."""
+    if out.requires_grad:
+        out.register_hook(_hip.kernel_ready)
+    return out
 
 
 def _masked(out, mask, x):
-    return out if mask is None else out * mask.view(x.shape[0], x.shape[1], 1).to(x.dtype)
+    return out if mask is None else out * mask.reshape(x.shape[0], x.shape[1], 1).to(x.dtype)
 
 
 def _graph_of(x, edge_index, layer=None):
@@ -73,18 +207,17 @@ def _no_attention_dropout(conv):
         raise NotImplementedError("attention dropout is not implemented: use dropout=0 or eval mode")
 
 
-def _dense_aggr(x, adj, mask, w_rel, w_root, bias, aggr):
+def _dense_aggr(conv, x, adj, mask, w_rel, w_root, bias, aggr):
     """The mean / max form of DenseGraphConv and DenseSAGEConv (csrc/aggrconv.hip).  Max reads only the
     pattern of adj, which then gets no gradient."""
-    x, adj = _dense_inputs(x, adj)
-    _hip.on_device(w_rel)
+    x, adj = _dense_contract(conv, x, adj, mask, conv.in_channels)
     out = _ops.dense_aggrconv(x, adj.detach() if aggr == "max" else adj, w_rel, w_root, bias, aggr)
     return _masked(out, mask, x)
 
 
-def _sparse_aggr(x, edge_index, edge_weight, w_rel, w_root, bias, aggr, name):
+def _sparse_aggr(conv, x, edge_index, edge_weight, w_rel, w_root, bias, aggr, name):
     """The mean / max form of GraphConv and SAGEConv (csrc/aggrconv.hip)."""
-    _hip.on_device(x, w_rel)        # a CPU call fails here, before the index is built
+    x, edge_index, edge_weight, _ = _sparse_contract(conv, x, edge_index, conv.in_channels, edge_weight=edge_weight)
     graph = _graph_of(x, edge_index, name)
     w = _csr_weights(edge_weight, graph)
     return _ops.csr_aggrconv(x, w, w_rel, w_root, bias, graph, aggr)
@@ -114,8 +247,9 @@ class DenseGraphConv(torch.nn.Module):
         if self.aggr != "add":
             if _act != _hip.ACT_NONE:
                 raise ValueError("activation fusion is available for aggr='add' only")
-            return _dense_aggr(x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_rel.bias, self.aggr)
-        x, adj = _dense_inputs(x, adj)
+            return _dense_aggr(self, x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_rel.bias,
+                               self.aggr)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         if mask is not None and _act != _hip.ACT_NONE:
             raise ValueError("activation fusion is not available together with a mask")
         out = _ops.dense_graphconv(x, adj, self.lin_rel.weight, self.lin_rel.bias,
@@ -153,8 +287,9 @@ class GraphConv(torch.nn.Module):
         if self.aggr != "add":
             if _act != _hip.ACT_NONE:
                 raise ValueError("activation fusion is available for aggr='add' only")
-            return _sparse_aggr(x, edge_index, edge_weight, self.lin_rel.weight, self.lin_root.weight,
+            return _sparse_aggr(self, x, edge_index, edge_weight, self.lin_rel.weight, self.lin_root.weight,
                                 self.lin_rel.bias, self.aggr, "GraphConv(aggr='%s')" % self.aggr)
+        x, edge_index, edge_weight, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_weight=edge_weight)
         graph = _graph_of(x, edge_index)
         w = _csr_weights(edge_weight, graph)
         return _ops.csr_graphconv(x, w, self.lin_rel.weight, self.lin_rel.bias,
@@ -192,8 +327,8 @@ class SAGEConv(torch.nn.Module):
             self.lin_r.reset_parameters()
 
     def forward(self, x, edge_index):
-        return _sparse_aggr(x, edge_index, None, self.lin_l.weight, self.lin_r.weight if self.root_weight else None,
-                            self.lin_l.bias, self.aggr, "SAGEConv")
+        return _sparse_aggr(self, x, edge_index, None, self.lin_l.weight,
+                            self.lin_r.weight if self.root_weight else None, self.lin_l.bias, self.aggr, "SAGEConv")
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, aggr={self.aggr})"
@@ -219,7 +354,7 @@ class DenseSAGEConv(torch.nn.Module):
         self.lin_root.reset_parameters()
 
     def forward(self, x, adj, mask=None):
-        return _dense_aggr(x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_root.bias, "mean")
+        return _dense_aggr(self, x, adj, mask, self.lin_rel.weight, self.lin_root.weight, self.lin_root.bias, "mean")
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
@@ -249,7 +384,7 @@ class DenseGCNConv(torch.nn.Module):
         _glorot_zero(self.lin, self.bias)
 
     def forward(self, x, adj, mask=None, add_loop=True):
-        x, adj = _dense_inputs(x, adj)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         out = _ops.dense_gcnconv(x, adj, self.lin.weight, self.bias, add_loop, 2.0 if self.improved else 1.0)
         return _masked(out, mask, x)
 
@@ -280,9 +415,8 @@ class GCNConv(torch.nn.Module):
         _glorot_zero(self.lin, self.bias)
 
     def forward(self, x, edge_index, edge_weight=None):
-        w = edge_weight
-        if w is not None and w.numel() != edge_index.shape[1]:
-            raise ValueError(f"edge_weight has {w.numel()} entries for {edge_index.shape[1]} edges")
+        x, edge_index, w, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_weight=edge_weight,
+                                               weight_per_edge=True)
         graph = _graph_of(x, edge_index, "GCNConv")
         w = _csr_weights(w, graph)     # unit weights without a gradient: the kernels count 1 per edge
         return _ops.csr_gcnconv(x, w, self.lin.weight, self.bias, graph, self.normalize,
@@ -328,9 +462,9 @@ class DenseGINConv(torch.nn.Module):
         self.eps.data.fill_(self.initial_eps)
 
     def forward(self, x, adj, mask=None, add_loop=True):
-        x, adj = _dense_inputs(x, adj)
+        x, adj = _dense_contract(self, x, adj, mask)
         h = _ops.dense_gin_aggregate(x, adj, self.eps, add_loop)
-        out = self.nn(h)
+        out = _ready_grad(self.nn(h))
         return _masked(out, mask, x)
 
     def __repr__(self):
@@ -354,9 +488,9 @@ class GINConv(torch.nn.Module):
         self.eps.data.fill_(self.initial_eps)
 
     def forward(self, x, edge_index):
-        _hip.on_device(x, self.eps)     # a CPU call fails here, before the index is built
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index)
         graph = _graph_of(x, edge_index, "GINConv")
-        return self.nn(_ops.csr_gin_aggregate(x, self.eps, graph))
+        return _ready_grad(self.nn(_ops.csr_gin_aggregate(x, self.eps, graph)))
 
     def __repr__(self):
         return f"{self.__class__.__name__}(nn={self.nn})"
@@ -409,7 +543,7 @@ class DenseGATConv(torch.nn.Module):
 
     def forward(self, x, adj, mask=None, add_loop=True):
         _no_attention_dropout(self)
-        x, adj = _dense_inputs(x, adj)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         out = _ops.dense_gatconv(x, adj.detach(), self.lin.weight, self.att_src, self.att_dst, self.bias,
                                  self.heads, self.concat, add_loop, self.negative_slope)
         return _masked(out, mask, x)
@@ -444,7 +578,7 @@ class GATConv(torch.nn.Module):
         if return_attention_weights is not None:
             raise NotImplementedError("GATConv(return_attention_weights=...) is not implemented")
         _no_attention_dropout(self)
-        _hip.on_device(self.lin.weight)     # a CPU module fails here, before the index is built
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_attr=edge_attr)
         graph = _graph_of(x, edge_index, "GATConv")
         return _ops.csr_gatconv(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.heads,
                                 self.concat, self.add_self_loops, self.negative_slope)
@@ -512,8 +646,7 @@ class DenseTransformerConv(torch.nn.Module):
 
     def forward(self, x, adj, mask=None, add_loop=False):
         _no_attention_dropout(self)
-        x, adj = _dense_inputs(x, adj)
-        _hip.on_device(self.lin_query.weight)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         w_all, b_all, w_beta = _transformer_operands(self)
         out = _ops.dense_transformerconv(x, adj.detach(), w_all, b_all, w_beta, self.heads, self.concat,
                                          self.root_weight, add_loop)
@@ -550,7 +683,7 @@ class TransformerConv(torch.nn.Module):
         if return_attention_weights is not None:
             raise NotImplementedError("TransformerConv(return_attention_weights=...) is not implemented")
         _no_attention_dropout(self)
-        _hip.on_device(self.lin_query.weight)     # a CPU module fails here, before the index is built
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_attr=edge_attr)
         graph = _graph_of(x, edge_index, "TransformerConv")
         w_all, b_all, w_beta = _transformer_operands(self)
         return _ops.csr_transformerconv(x, w_all, b_all, w_beta, graph, self.heads, self.concat, self.root_weight)
@@ -614,8 +747,7 @@ class DenseResGatedGraphConv(torch.nn.Module):
         _resgated_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=False):
-        x, adj = _dense_inputs(x, adj)
-        _hip.on_device(self.lin_key.weight)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         w_all, b_all = _resgated_operands(self)
         out = _ops.dense_resgatedconv(x, adj, w_all, b_all, self.bias, self.root_weight, add_loop)
         return _masked(out, mask, x)
@@ -646,7 +778,7 @@ class ResGatedGraphConv(torch.nn.Module):
         _resgated_reset(self)
 
     def forward(self, x, edge_index, edge_attr=None):
-        _hip.on_device(self.lin_key.weight)     # a CPU call fails here, before the index is built
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_attr=edge_attr)
         graph = _graph_of(x, edge_index, "ResGatedGraphConv")
         w_all, b_all = _resgated_operands(self)
         return _ops.csr_resgatedconv(x, w_all, b_all, self.bias, graph, self.root_weight)
@@ -668,12 +800,6 @@ def _gated_reset(conv):
     bound = 1.0 / conv.out_channels ** 0.5      # PyG's uniform(out_channels, weight)
     torch.nn.init.uniform_(conv.weight, -bound, bound)
     conv.rnn.reset_parameters()
-
-
-def _gated_width(conv, x):
-    if x.shape[-1] > conv.out_channels:
-        raise ValueError("The number of input channels is not allowed to be larger than the number of output "
-                         "channels")
 
 
 def _gated_cell(conv):
@@ -701,9 +827,7 @@ class DenseGatedGraphConv(torch.nn.Module):
         _gated_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=False):
-        x, adj = _dense_inputs(x, adj)
-        _gated_width(self, x)
-        _hip.on_device(self.weight)
+        x, adj = _dense_contract(self, x, adj, mask, max_channels=self.out_channels)
         out = _ops.dense_gatedgraphconv(x, adj, self.weight, *_gated_cell(self), add_loop)
         return _masked(out, mask, x)
 
@@ -732,8 +856,8 @@ class GatedGraphConv(torch.nn.Module):
         _gated_reset(self)
 
     def forward(self, x, edge_index, edge_weight=None):
-        _gated_width(self, x)
-        _hip.on_device(x, self.weight)     # a CPU call fails here, before the index is built
+        x, edge_index, edge_weight, _ = _sparse_contract(self, x, edge_index, edge_weight=edge_weight,
+                                                         max_channels=self.out_channels)
         graph = _graph_of(x, edge_index, "GatedGraphConv")
         w = _csr_weights(edge_weight, graph)
         return _ops.csr_gatedgraphconv(x, w, self.weight, *_gated_cell(self), graph)
@@ -788,8 +912,7 @@ class DenseTAGConv(torch.nn.Module):
         _tag_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=False):
-        x, adj = _dense_inputs(x, adj)
-        _hip.on_device(self.lins[0].weight)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         out = _ops.dense_tagconv(x, adj, _tag_weight(self), self.bias, self.normalize, add_loop)
         return _masked(out, mask, x)
 
@@ -819,7 +942,7 @@ class TAGConv(torch.nn.Module):
         _tag_reset(self)
 
     def forward(self, x, edge_index, edge_weight=None):
-        _hip.on_device(x, self.lins[0].weight)     # a CPU call fails here, before the index is built
+        x, edge_index, edge_weight, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_weight=edge_weight)
         graph = _graph_of(x, edge_index, "TAGConv")
         w = _csr_weights(edge_weight, graph)
         return _ops.csr_tagconv(x, w, _tag_weight(self), self.bias, graph, self.normalize)
@@ -938,7 +1061,7 @@ def _pna_tail(conv, h):
         return h
     Fo = conv.F_out
     hs = [seq[1:](h[..., t * Fo:(t + 1) * Fo]) for t, seq in enumerate(conv.post_nns)]
-    return conv.lin(torch.cat(hs, -1))
+    return _ready_grad(conv.lin(torch.cat(hs, -1)))
 
 
 _PNA_DOC = """Per tower t (x_t: the tower's in_channels / towers columns of x with divide_input, else all of x): the
@@ -977,8 +1100,7 @@ class DensePNAConv(torch.nn.Module):
         _pna_reset(self)
 
     def forward(self, x, adj, mask=None, add_loop=False):
-        x, adj = _dense_inputs(x, adj)
-        _hip.on_device(self.lin.weight)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         h = _ops.dense_pnaconv(x, adj.detach(), *_pna_operands(self), self._cfg, add_loop)
         return _masked(_pna_tail(self, h), mask, x)
 
@@ -1008,7 +1130,7 @@ class PNAConv(torch.nn.Module):
         _pna_reset(self)
 
     def forward(self, x, edge_index, edge_attr=None):
-        _hip.on_device(x, self.lin.weight)     # a CPU call fails here, before the index is built
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, self.in_channels, edge_attr=edge_attr)
         graph = _graph_of(x, edge_index, "PNAConv")
         return _pna_tail(self, _ops.csr_pnaconv(x, *_pna_operands(self), graph, self._cfg))
 
@@ -1115,12 +1237,8 @@ class DenseRGCNConv(torch.nn.Module):
         _rgcn_reset(self)
 
     def forward(self, x, adj, rel, mask=None):
-        x, adj = _dense_inputs(x, adj)
+        x, adj, rel = _dense_contract(self, x, adj, mask, self.in_channels, planes=[("rel", rel)])
         rel = _rgcn_codes(rel, "rel")
-        rel = rel.unsqueeze(0) if rel.dim() == 2 else rel
-        if rel.shape[0] != x.shape[0]:
-            rel = rel.expand(x.shape[0], -1, -1)
-        _hip.on_device(x, self.weight)     # a CPU call fails here
         out = _ops.dense_rgcnconv(x, adj, rel.detach().to(torch.float32), _rgcn_weight(self), self.root, self.bias,
                                   self.aggr == "mean")
         return _masked(out, mask, x)
@@ -1149,7 +1267,9 @@ class RGCNConv(torch.nn.Module):
         _rgcn_reset(self)
 
     def forward(self, x, edge_index, edge_type):
-        _hip.on_device(x, self.weight)     # a CPU call fails here, before the index is built
+        x, edge_index, _, edge_type = _sparse_contract(
+            self, x, edge_index, self.in_channels, edge_type=edge_type,
+            type_dtypes=_CODE_DTYPES if self.relation_mask else _I64)
         graph = _graph_of(x, edge_index, "RGCNConv")
         if edge_type is None or edge_type.numel() != graph.E:
             raise ValueError(f"RGCNConv: edge_type must hold one entry per edge ({graph.E})")
@@ -1244,9 +1364,6 @@ def _gen_reset(conv):
 
 def _gen_source(conv, x):
     """xs, what the aggregation kernels read: lin_src(x), or x itself when the widths agree."""
-    _hip.on_device(x, conv.aggr_module.t)   # a CPU call fails here, before any torch module runs
-    if x.dtype != torch.float32:
-        raise TypeError("x must be float32; got %s" % x.dtype)
     return conv.lin_src(x) if hasattr(conv, "lin_src") else x
 
 
@@ -1255,7 +1372,7 @@ def _gen_tail(conv, x, agg):
     if hasattr(conv, "msg_norm"):
         agg = conv.msg_norm(x, agg)
     out = agg + (conv.lin_dst(x) if hasattr(conv, "lin_dst") else x)
-    return conv.mlp(out.reshape(-1, conv.out_channels)).view(*out.shape[:-1], conv.out_channels)
+    return _ready_grad(conv.mlp(out.reshape(-1, conv.out_channels)).view(*out.shape[:-1], conv.out_channels))
 
 
 _GEN_DOC = """m = relu(xs) + eps with xs = lin_src(x) (x itself when in_channels == out_channels); per channel c a
@@ -1293,7 +1410,7 @@ class DenseGENConv(torch.nn.Module):
         _gen_reset(self)
 
     def forward(self, x, adj, mask=None):
-        x, adj = _dense_inputs(x, adj)
+        x, adj = _dense_contract(self, x, adj, mask, self.in_channels)
         agg = _ops.dense_genagg(_gen_source(self, x), adj, self.aggr_module.t, self.eps)
         return _masked(_gen_tail(self, x, agg), mask, x)
 
@@ -1320,6 +1437,7 @@ class GENConv(torch.nn.Module):
         _gen_reset(self)
 
     def forward(self, x, edge_index):
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, self.in_channels)
         xs = _gen_source(self, x)
         graph = _graph_of(x, edge_index, "GENConv")
         return _gen_tail(self, x, _ops.csr_genagg(xs, self.aggr_module.t, graph, self.eps))
@@ -1344,16 +1462,18 @@ def _edge_init(conv, name, nn, aggr):
     conv.in_channels, conv.out_channels = nn[0].in_features // 2, nn[2].out_features
 
 
+def _edge_width(conv):
+    """in_channels as nn[0] has it now, and the wording of a mismatch, for the calling contract."""
+    two_f = conv.nn[0].in_features
+    return dict(in_channels=two_f / 2, width_error=lambda F: f"nn[0] takes {two_f} features, but [x_i, x_j - x_i] "
+                                                             f"has 2 * {F}")
+
+
 def _edge_terms(conv, x):
     """(P, Q, W2, b2, slope): the first Linear as two node-level products (torch), W1 = [A | Bm]:
     W1 [x_i, x_j - x_i] + b1 = P_i + Q_j with P = x (A - Bm)^T + b1, Q = x Bm^T."""
     lin1, act, lin2 = conv.nn[0], conv.nn[1], conv.nn[2]
     F = x.shape[-1]
-    if lin1.in_features != 2 * F:
-        raise ValueError(f"nn[0] takes {lin1.in_features} features, but [x_i, x_j - x_i] has 2 * {F}")
-    _hip.on_device(x, lin2.weight)          # a CPU call fails here, before any torch op runs
-    if x.dtype != torch.float32:
-        raise TypeError("x must be float32; got %s" % x.dtype)
     A, Bm = lin1.weight[:, :F], lin1.weight[:, F:]
     P = torch.nn.functional.linear(x, A - Bm, lin1.bias)
     Q = torch.nn.functional.linear(x, Bm)
@@ -1392,7 +1512,7 @@ class DenseEdgeConv(torch.nn.Module):
         _gin_reset(self.nn)
 
     def forward(self, x, adj, mask=None):
-        x, adj = _dense_inputs(x, adj)
+        x, adj = _dense_contract(self, x, adj, mask, **_edge_width(self))
         P, Q, w2, b2, slope = _edge_terms(self, x)
         return _masked(_ops.dense_edgemax(P, Q, adj, w2, b2, slope), mask, x)
 
@@ -1416,6 +1536,7 @@ class EdgeConv(torch.nn.Module):
         _gin_reset(self.nn)
 
     def forward(self, x, edge_index):
+        x, edge_index, _, _ = _sparse_contract(self, x, edge_index, **_edge_width(self))
         P, Q, w2, b2, slope = _edge_terms(self, x)
         graph = _graph_of(x, edge_index, "EdgeConv")
         return _ops.csr_edgemax(P, Q, w2, b2, slope, graph)
