@@ -11,7 +11,7 @@
 // workgroup, K in tiles of 32 staged through LDS with zero padding, masked stores) with the self term added in the
 // epilogue: one launch for h, the same kernel with the adjacency read transposed for g_x.  g_adj is gcn_mm.h's
 // k_gcn_mm as it is.  g_eps: fp64 partial sums of fixed element ranges into the workspace, summed in a fixed order by
-// one workgroup - deterministic, no atomics.  F <= 128; any N.
+// one workgroup (fixed_sum.h's dot_sum) - deterministic, no atomics.  F <= 128; any N.
 #include "fixed_sum.h"
 #include "gcn_mm.h"
 
@@ -70,45 +70,6 @@ __global__ __launch_bounds__(256) void k_gin_gather(const float* __restrict__ sr
     for (int64_t k = ptr[i]; k < k1; ++k) a += src[(size_t)idx[k] * F + f];
   }
   out[t] = fmaf(1.f + eps[0], src[t], a);
-}
-
-// g_eps, pass 1: part[blk] = sum of a[e] b[e] over the block's element range [blk * chunk, (blk + 1) * chunk), in
-// fp64 (every product exact), lanes and waves combined in a fixed order; pass 2 is fixed_sum.h's sum_parts
-constexpr int DOT_BLOCKS = 1024;  // at most; chunk a multiple of 256
-
-__global__ __launch_bounds__(256) void k_gin_dot_parts(const float* __restrict__ a, const float* __restrict__ b,
-                                                       int64_t L, int64_t chunk, double* __restrict__ part) {
-  __shared__ double sp[256];
-  const int64_t e0 = (int64_t)blockIdx.x * chunk;
-  const int64_t e1 = min(L, e0 + chunk);
-  double s = 0.0;
-  for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) s += (double)a[e] * (double)b[e];
-  const double total = block_sum(s, sp);
-  if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-
-void dot_plan(int64_t L, int* nblocks, int64_t* chunk) {
-  int64_t c = (L + DOT_BLOCKS - 1) / DOT_BLOCKS;
-  c = std::max<int64_t>((c + 255) / 256 * 256, 4096);
-  *chunk = c;
-  *nblocks = (int)((L + c - 1) / c);
-}
-
-size_t dot_ws_bytes(int64_t L) {
-  int n;
-  int64_t c;
-  dot_plan(L, &n, &c);
-  return align256((size_t)n * sizeof(double));
-}
-
-int dot_sum(const float* a, const float* b, int64_t L, float* out, void* workspace, hipStream_t s) {
-  int n;
-  int64_t c;
-  dot_plan(L, &n, &c);
-  double* part = (double*)workspace;
-  hipLaunchKernelGGL(k_gin_dot_parts, dim3(n), dim3(256), 0, s, a, b, L, c, part);
-  const int rc = gcm_launch_status();
-  return rc ? rc : sum_parts(part, n, out, s);
 }
 
 }  // namespace

@@ -34,6 +34,10 @@ _RESET_HEADER = _abi.header("gcm_hip_reset.h")
 RESET_PROTOTYPES = _abi.prototypes(_RESET_HEADER)
 # and the section from gcm_hip_gin.h (the aggregation of GINConv / DenseGINConv and its gradients)
 GIN_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_gin.h"))
+# and the section from gcm_hip_gine.h (the aggregation of GINEConv / DenseGINEConv, and RelativeEdgeAttr)
+_GINE_HEADER = _abi.header("gcm_hip_gine.h")
+GINE_PROTOTYPES = _abi.prototypes(_GINE_HEADER)
+_CONSTANTS.update(_abi.constants(_GINE_HEADER))
 # and the section from gcm_hip_bptt_hops.h (the GEMM-form backward of forward-hop cached chains)
 BPTT_HOPS_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_bptt_hops.h"))
 # and the section from gcm_hip_bptt_hops_unfolded.h (that backward before the hop sum was folded into its products: the A/B)
@@ -122,6 +126,7 @@ def lib():
         bind(handle, TRANSFORMER_PROTOTYPES)
         bind(handle, RESET_PROTOTYPES)
         bind(handle, GIN_PROTOTYPES)
+        bind(handle, GINE_PROTOTYPES)
         bind(handle, BPTT_HOPS_PROTOTYPES)
         bind(handle, BPTT_HOPS_UNFOLDED_PROTOTYPES)
         bind(handle, RESGATED_PROTOTYPES)

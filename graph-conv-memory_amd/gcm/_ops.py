@@ -1048,6 +1048,181 @@ def csr_gin_aggregate(x, eps, graph):
 
 
 # ---------------------------------------------------------------------------
+# DenseGINEConv / GINEConv and RelativeEdgeAttr (csrc/gineconv.hip): the aggregation alone, `nn` stays in torch.  The
+# projected edge features and the messages are never materialised: what is saved is the inputs.
+# ---------------------------------------------------------------------------
+def _gine_lin(w_e, b_e, F, D):
+    if w_e is None:
+        assert b_e is None and D == F
+        return None, None
+    w_e, b_e = w_e.contiguous(), b_e.contiguous()
+    assert w_e.shape == (F, D) and b_e.shape == (F,)
+    return w_e, b_e
+
+
+class _CsrGINEAggregate(torch.autograd.Function):
+    """h_i = (1 + eps) x_i + sum over the in-edges k of i of relu(x_source + e_k), e_k = w_e a_k + b_e (a_k itself
+    when w_e is None); x [M,F], edge_attr [E,D] in the order of graph.edge_index, eps [1] (read on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, edge_attr, w_e, b_e, eps, graph):
+        x, edge_attr, eps = x.contiguous(), edge_attr.contiguous(), eps.contiguous()
+        M, F = x.shape
+        E, D = edge_attr.shape
+        w_e, b_e = _gine_lin(w_e, b_e, F, D)
+        _hip.on_device(x, edge_attr, w_e, b_e, eps)
+        assert M == graph.M and E == graph.E
+        assert eps.numel() == 1 and eps.dtype == _f32
+        h = torch.empty(M, F, device=x.device, dtype=_f32)
+        _call("gcm_csr_gine_fwd", _hip.ptr(x), _hip.ptr(edge_attr), _hip.ptr(w_e), _hip.ptr(b_e), _hip.ptr(eps),
+              _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(graph.csr_perm), _hip.ptr(h), M, E, F, D,
+              _hip.stream())
+        ctx.save_for_backward(x, edge_attr, w_e, b_e, eps)
+        ctx.graph = graph
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        x, edge_attr, w_e, b_e, eps = ctx.saved_tensors
+        graph = ctx.graph
+        M, F = x.shape
+        E, D = edge_attr.shape
+        need_x, need_ea, need_w, need_b, need_eps, _ = ctx.needs_input_grad
+        g_h = _hip.kernel_ready(g_h)
+        dev = x.device
+        col_ptr = rows = csc_perm = None
+        if need_x and E > 0:
+            by_source = Segments.by_source(graph)
+            col_ptr, rows, csc_perm = by_source.ptr, graph.csc()[1], by_source.perm
+        g_x = torch.empty_like(x) if need_x else None
+        g_ea = torch.empty_like(edge_attr) if need_ea else None
+        g_w = torch.empty_like(w_e) if need_w else None
+        g_b = torch.empty_like(b_e) if need_b else None
+        g_eps = torch.empty_like(eps) if need_eps else None
+        ws, ws_bytes = _scratch("gcm_csr_gine_bwd", M, E, F, D, device=dev)
+        _call("gcm_csr_gine_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(edge_attr), _hip.ptr(w_e), _hip.ptr(b_e),
+              _hip.ptr(eps), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(graph.csr_perm),
+              _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(csc_perm), _hip.ptr(g_x), _hip.ptr(g_ea), _hip.ptr(g_w),
+              _hip.ptr(g_b), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, M, E, F, D, _hip.stream())
+        return g_x, g_ea, g_w, g_b, g_eps, None
+
+
+def csr_gine_aggregate(x, edge_attr, w_e, b_e, eps, graph):
+    return _CsrGINEAggregate.apply(x, edge_attr, w_e, b_e, eps, graph)
+
+
+class _DenseGINEAggregate(torch.autograd.Function):
+    """h = s x + sum_j adj_ij relu(x_j + e_ij) over the set entries of adj, s = 1 + eps if add_loop else 0; x [B,N,F],
+    adj [B,N,N], edge_attr [B,N,N,D].  With a gradient wanted for adj, the backward reads every entry of edge_attr."""
+
+    @staticmethod
+    def forward(ctx, x, adj, edge_attr, w_e, b_e, eps, add_loop):
+        x, adj, edge_attr, eps = x.contiguous(), adj.contiguous(), edge_attr.contiguous(), eps.contiguous()
+        B, N, F = x.shape
+        D = edge_attr.shape[-1]
+        w_e, b_e = _gine_lin(w_e, b_e, F, D)
+        _hip.on_device(x, adj, edge_attr, w_e, b_e, eps)
+        assert adj.shape == (B, N, N) and edge_attr.shape == (B, N, N, D)
+        assert eps.numel() == 1 and eps.dtype == _f32
+        h = torch.empty(B, N, F, device=x.device, dtype=_f32)
+        saved, saved_bytes = _scratch("gcm_dense_gine_fwd", B, N, F, D, device=x.device)
+        _call("gcm_dense_gine_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(edge_attr), _hip.ptr(w_e), _hip.ptr(b_e),
+              _hip.ptr(eps), _hip.ptr(h), _hip.ptr(saved), saved_bytes, B, N, F, D, int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, adj, edge_attr, w_e, b_e, eps, saved)
+        ctx.add_loop = int(add_loop)
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        x, adj, edge_attr, w_e, b_e, eps, saved = ctx.saved_tensors
+        B, N, F = x.shape
+        D = edge_attr.shape[-1]
+        need_x, need_adj, need_ea, need_w, need_b, need_eps, _ = ctx.needs_input_grad
+        g_h = _hip.kernel_ready(g_h)
+        g_x = torch.empty_like(x) if need_x else None
+        g_adj = torch.empty_like(adj) if need_adj else None
+        g_ea = torch.empty_like(edge_attr) if need_ea else None
+        g_w = torch.empty_like(w_e) if need_w else None
+        g_b = torch.empty_like(b_e) if need_b else None
+        g_eps = torch.empty_like(eps) if need_eps else None
+        ws, ws_bytes = _scratch("gcm_dense_gine_bwd", B, N, F, D, device=x.device)
+        _call("gcm_dense_gine_bwd", _hip.ptr(g_h), _hip.ptr(x), _hip.ptr(adj), _hip.ptr(edge_attr), _hip.ptr(w_e),
+              _hip.ptr(b_e), _hip.ptr(eps), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_adj), _hip.ptr(g_ea),
+              _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_eps), _hip.ptr(ws), ws_bytes, B, N, F, D, ctx.add_loop,
+              _hip.stream())
+        return g_x, g_adj, g_ea, g_w, g_b, g_eps, None
+
+
+def dense_gine_aggregate(x, adj, edge_attr, w_e, b_e, eps, add_loop):
+    return _DenseGINEAggregate.apply(x, adj, edge_attr, w_e, b_e, eps, add_loop)
+
+
+class _RelEdgeAttr(torch.autograd.Function):
+    """out [E,D] in edge_index order: [(sink - source) * time_scale, x[source, p0:p0+P] - x[sink, p0:p0+P]]; the
+    gradient to x is gathered over the CSC column and the CSR row of every node (`graph`: the list's GraphIndex)."""
+
+    @staticmethod
+    def forward(ctx, x, edge_index, graph, p0, P, time, time_scale):
+        x, edge_index = x.contiguous(), edge_index.contiguous()
+        _hip.on_device(x, edge_index)
+        M, F = x.shape
+        E = edge_index.shape[1]
+        out = torch.empty(E, time + P, device=x.device, dtype=_f32)
+        _call("gcm_rel_edge_attr_fwd", _hip.ptr(x), _hip.ptr(edge_index), _hip.ptr(out), M, E, F, p0, P, time,
+              float(time_scale), _hip.stream())
+        ctx.graph, ctx.cfg = graph, (M, E, F, p0, P, time)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        M, E, F, p0, P, time = ctx.cfg
+        graph = ctx.graph
+        g_out = _hip.kernel_ready(g_out)
+        g_x = torch.empty(M, F, device=g_out.device, dtype=_f32)
+        col_ptr = csc_perm = None
+        if E > 0:
+            by_source = Segments.by_source(graph)
+            col_ptr, csc_perm = by_source.ptr, by_source.perm
+        _call("gcm_rel_edge_attr_bwd", _hip.ptr(g_out), _hip.ptr(graph.row_ptr), _hip.ptr(graph.csr_perm),
+              _hip.ptr(col_ptr), _hip.ptr(csc_perm), _hip.ptr(g_x), M, E, F, p0, P, time, _hip.stream())
+        return g_x, None, None, None, None, None, None
+
+
+def rel_edge_attr(x, edge_index, graph, p0, P, time, time_scale):
+    """graph: a callable that returns the list's GraphIndex, called only when x needs a gradient through the pose."""
+    if P == 0 or not (x.requires_grad and torch.is_grad_enabled()):
+        return _RelEdgeAttr.apply(x.detach(), edge_index, None, p0, P, time, time_scale)
+    return _RelEdgeAttr.apply(x, edge_index, graph(), p0, P, time, time_scale)
+
+
+class _DenseRelEdgeAttr(torch.autograd.Function):
+    """out [B,N,N,D]: entry (b,i,j) = [(i - j) * time_scale, x[b,j,p0:p0+P] - x[b,i,p0:p0+P]]."""
+
+    @staticmethod
+    def forward(ctx, x, p0, P, time, time_scale):
+        x = x.contiguous()
+        _hip.on_device(x)
+        B, N, F = x.shape
+        out = torch.empty(B, N, N, time + P, device=x.device, dtype=_f32)
+        _call("gcm_dense_rel_edge_attr_fwd", _hip.ptr(x), _hip.ptr(out), B, N, F, p0, P, time, float(time_scale),
+              _hip.stream())
+        ctx.cfg = (B, N, F, p0, P, time)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        B, N, F, p0, P, time = ctx.cfg
+        g_out = _hip.kernel_ready(g_out)
+        g_x = torch.empty(B, N, F, device=g_out.device, dtype=_f32)
+        _call("gcm_dense_rel_edge_attr_bwd", _hip.ptr(g_out), _hip.ptr(g_x), B, N, F, p0, P, time, _hip.stream())
+        return g_x, None, None, None, None
+
+
+def dense_rel_edge_attr(x, p0, P, time, time_scale):
+    return _DenseRelEdgeAttr.apply(x.detach() if P == 0 else x, p0, P, time, time_scale)
+
+
+# ---------------------------------------------------------------------------
 # DenseGATConv / GATConv (PyG, GAT v1; csrc/gatconv.hip)
 # ---------------------------------------------------------------------------
 class _DenseGATConv(torch.autograd.Function):

@@ -83,10 +83,23 @@ def _check_width(layer, F, in_channels, max_channels, width_error):
                          "output channels")
 
 
+def _check_edge_attr(layer, edge_attr, lead, width, width_error):
+    """edge_attr of a layer that reads it (`edge_attr_width`): `lead` = the accepted leading shapes, then `width`
+    features."""
+    s = tuple(edge_attr.shape)
+    if len(s) < 2 or s[:-1] not in lead:
+        want = " or ".join(str(list(l) + ["D"]).replace("'", "") for l in lead)
+        raise ValueError(f"{layer}: edge_attr must be {want}; got {list(s)}")
+    if s[-1] != width:
+        raise ValueError(width_error or f"{layer}: edge_attr has {s[-1]} features, the layer has edge_dim={width}")
+
+
 def _dense_contract(conv, x, adj, mask=None, in_channels=None, planes=(), device=True, width_error=None,
-                    max_channels=None):
+                    max_channels=None, edge_attr=None, edge_attr_width=None, edge_attr_error=None):
     """The calling contract of the dense layers, checked before anything else runs -> (x [B,N,F], adj [B,N,N], *planes
-    [B,N,N]) as the kernels read them.  In this order, so that the first two fail alike on a machine without a GPU:
+    [B,N,N]) as the kernels read them.  With `edge_attr_width` (a layer that reads edge features: DenseGINEConv),
+    edge_attr [B,N,N,D], [1,N,N,D] or [N,N,D] with D == edge_attr_width is checked and made ready like adj and comes
+    back last (`edge_attr_error`: the layer's own wording of a wrong D).  In this order, so that the first two fail alike on a machine without a GPU:
     1. dtype (TypeError): x, adj and every floating parameter and buffer float32, mask bool or float32, `planes`
        ((name, tensor) pairs of adj's shape: RGCN's relation codes) float32 or int64.  Nothing is cast.
     2. shape (ValueError): x [B,N,F] or [N,F], F == in_channels or F <= max_channels when one is given; adj and the
@@ -101,6 +114,8 @@ def _dense_contract(conv, x, adj, mask=None, in_channels=None, planes=(), device
     planes = list(planes)
     operands = [("x", x, _F32), ("adj", adj, _F32), ("mask", mask, _MASK_DTYPES)]
     operands += [(name, t, _CODE_DTYPES) for name, t in planes]
+    if edge_attr_width is not None:
+        operands.append(("edge_attr", edge_attr, _F32))
     state = _state(conv)
     _check_dtypes(layer, state, operands)
     xs = tuple(x.shape)
@@ -115,17 +130,23 @@ def _dense_contract(conv, x, adj, mask=None, in_channels=None, planes=(), device
                              f"got {list(s)}")
     if mask is not None and mask.numel() != B * N:
         raise ValueError(f"{layer}: mask must hold B * N = {B * N} entries; got {list(mask.shape)}")
+    if edge_attr_width is not None:
+        _check_edge_attr(layer, edge_attr, [(B, N, N), (1, N, N), (N, N)], edge_attr_width, edge_attr_error)
     if device:
         _check_devices(layer, state, operands)
     out = [_hip.kernel_ready(x.unsqueeze(0) if len(xs) == 2 else x)]
     for _, t in [("adj", adj)] + planes:
         t = t.unsqueeze(0) if t.dim() == 2 else t
         out.append(_hip.kernel_ready(t.expand(B, -1, -1) if t.shape[0] != B else t))
+    if edge_attr_width is not None:
+        t = edge_attr.unsqueeze(0) if edge_attr.dim() == 3 else edge_attr
+        out.append(_hip.kernel_ready(t.expand(B, -1, -1, -1) if t.shape[0] != B else t))
     return out
 
 
 def _sparse_contract(conv, x, edge_index, in_channels=None, edge_weight=None, edge_attr=None, edge_type=None,
-                     type_dtypes=_I64, device=True, width_error=None, weight_per_edge=False, max_channels=None):
+                     type_dtypes=_I64, device=True, width_error=None, weight_per_edge=False, max_channels=None,
+                     edge_attr_width=None, edge_attr_error=None):
     """The calling contract of the sparse layers, checked before anything else runs -> (x [M,F], edge_index [2,E],
     edge_weight, edge_type) as the kernels and the indexing read them.  Steps and order as _dense_contract:
     1. dtype (TypeError): x, edge_weight, edge_attr and every floating parameter and buffer float32; edge_index
@@ -137,7 +158,10 @@ def _sparse_contract(conv, x, edge_index, in_channels=None, edge_weight=None, ed
     4. layout: any strides go (`pairs.t()` of an [E,2] list, a slice of a wider buffer).  What comes back is
        contiguous and 16-byte aligned (_hip.kernel_ready): a copy where the operand was not, the operand itself where
        it was.  An edge_index that carries a `gcm_graph` for these M nodes comes back as it is: the index is the
-       library's own and the list is not read again.  edge_attr is ignored by every layer here and is not copied.
+       library's own and the list is not read again.  edge_attr is ignored and not copied by every layer but one
+       that reads edge features and says so with `edge_attr_width` (GINEConv): then edge_attr must be [E,D] with D ==
+       edge_attr_width (step 2; `edge_attr_error`: the layer's own wording of a wrong D), is made ready like x and
+       comes back as a fifth value.
     Not checked: node ids in edge_index outside [0, M) (finding them takes a pass over the list and a device
     synchronisation), and the alignment of the parameters.  `device=False` skips step 3 alone."""
     layer = type(conv).__name__
@@ -153,6 +177,8 @@ def _sparse_contract(conv, x, edge_index, in_channels=None, edge_weight=None, ed
         raise ValueError(f"{layer}: edge_index must be [2,E] = (source, sink); got {list(es)}")
     if weight_per_edge and edge_weight is not None and edge_weight.numel() != es[1]:
         raise ValueError(f"{layer}: edge_weight has {edge_weight.numel()} entries for {es[1]} edges")
+    if edge_attr_width is not None:
+        _check_edge_attr(layer, edge_attr, [(es[1],)], edge_attr_width, edge_attr_error)
     if device:
         _check_devices(layer, state, operands)
     graph = getattr(edge_index, "gcm_graph", None)
@@ -161,7 +187,8 @@ def _sparse_contract(conv, x, edge_index, in_channels=None, edge_weight=None, ed
     w = _hip.kernel_ready(edge_weight)
     if w is not edge_weight and getattr(edge_weight, "gcm_unit_weights", False):
         w.gcm_unit_weights = True
-    return _hip.kernel_ready(x), edge_index, w, _hip.kernel_ready(edge_type)
+    out = _hip.kernel_ready(x), edge_index, w, _hip.kernel_ready(edge_type)
+    return out if edge_attr_width is None else out + (_hip.kernel_ready(edge_attr),)
 
 
 def _ready_grad(out):
