@@ -1223,6 +1223,149 @@ def dense_rel_edge_attr(x, p0, P, time, time_scale):
 
 
 # ---------------------------------------------------------------------------
+# GATv2Conv / DenseGATv2Conv (gcm.gatv2; csrc/gatv2conv.hip).  Nothing per edge is saved: x_l, x_r and the softmax's
+# per-row maximum and sum are, and the backward recomputes the scores from them.
+# ---------------------------------------------------------------------------
+class GATv2Config:
+    """What the kernels take beside tensors: heads, out_channels, concat, loops (add_self_loops / add_loop),
+    fill_value ("mean" or a number) and negative_slope."""
+
+    def __init__(self, heads, out_channels, concat, loops, fill_value, slope):
+        self.H, self.C, self.concat, self.loops = int(heads), int(out_channels), int(bool(concat)), int(bool(loops))
+        self.fill_mean = int(fill_value == "mean")
+        self.fill = 0.0 if self.fill_mean else float(fill_value)
+        self.slope = float(slope)
+
+    def tail(self):
+        return (self.concat, self.loops, self.fill_mean, self.fill, self.slope, _hip.stream())
+
+
+def _gatv2_operands(cfg, x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr):
+    """Contiguous operands, checked against each other -> (operands, Fi, D)."""
+    ops = [_contig(t) for t in (x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr)]
+    x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr = ops
+    _hip.on_device(*ops)
+    Fi, HC = x.shape[-1], cfg.H * cfg.C
+    assert w_l.shape == (HC, Fi) and att.numel() == HC
+    assert w_r is None or w_r.shape == (HC, Fi)
+    assert w_r is not None or b_r is None
+    D = 0 if w_e is None else w_e.shape[1]
+    assert w_e is None or (w_e.shape == (HC, D) and edge_attr is not None and edge_attr.shape[-1] == D)
+    return ops, Fi, D
+
+
+def _gatv2_grads(ctx, cfg, x, w_l, w_r, w_e, edge_attr):
+    """The outputs the backward call is to fill (None: skip), in the order of the forward's inputs."""
+    need = ctx.needs_input_grad
+    HC, dev = cfg.H * cfg.C, x.device
+    new = lambda wanted, like=None, n=None: (None if not wanted else torch.empty_like(like) if like is not None
+                                             else torch.empty(n, device=dev, dtype=_f32))
+    return [new(need[0], x), new(need[1], w_l), new(need[2], n=HC), new(need[3], w_r), new(need[4], n=HC),
+            new(need[5], n=HC), new(need[6], w_e), new(need[7], n=HC if cfg.concat else cfg.C),
+            new(need[8], edge_attr)]
+
+
+class _CsrGATv2Conv(torch.autograd.Function):
+    """x [M,Fi], edge_attr [E,D] in the order of graph.edge_index (None without edge features), w_r None: shared."""
+
+    @staticmethod
+    def forward(ctx, x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr, graph, cfg):
+        ops, Fi, D = _gatv2_operands(cfg, x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr)
+        x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr = ops
+        M, E, H, C = x.shape[0], graph.E, cfg.H, cfg.C
+        assert M == graph.M and (edge_attr is None or edge_attr.shape[0] == E)
+        dev = x.device
+        out = torch.empty(M, H * C if cfg.concat else C, device=dev, dtype=_f32)
+        xl = torch.empty(M, H * C, device=dev, dtype=_f32)
+        xr = torch.empty(M, H * C, device=dev, dtype=_f32) if w_r is not None else None
+        stats = torch.empty(2, M, H, device=dev, dtype=_f32)          # row max, row sum
+        ws, ws_bytes = _scratch("gcm_csr_gatv2_fwd", M, H, C, cfg.concat, device=dev)
+        _call("gcm_csr_gatv2_fwd", _hip.ptr(x), _hip.ptr(w_l), _hip.ptr(b_l), _hip.ptr(w_r), _hip.ptr(b_r),
+              _hip.ptr(att), _hip.ptr(w_e), _hip.ptr(bias), _hip.ptr(edge_attr), _hip.ptr(graph.row_ptr),
+              _hip.ptr(graph.col), _hip.ptr(graph.csr_perm), _hip.ptr(out), _hip.ptr(xl), _hip.ptr(xr),
+              _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(ws), ws_bytes, M, E, Fi, H, C, D, *cfg.tail())
+        ctx.save_for_backward(x, w_l, w_r, att, w_e, edge_attr, xl, xr, stats)
+        ctx.graph, ctx.cfg = graph, cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_l, w_r, att, w_e, edge_attr, xl, xr, stats = ctx.saved_tensors
+        graph, cfg = ctx.graph, ctx.cfg
+        M, Fi = x.shape
+        E, D = graph.E, 0 if w_e is None else w_e.shape[1]
+        g_out = _hip.kernel_ready(g_out)
+        need = ctx.needs_input_grad
+        col_ptr = rows = csc_perm = None
+        if E > 0 and (need[0] or need[1] or need[2]):
+            by_source = Segments.by_source(graph)
+            col_ptr, rows, csc_perm = by_source.ptr, graph.csc()[1], by_source.perm
+        g = _gatv2_grads(ctx, cfg, x, w_l, w_r, w_e, edge_attr)
+        g_x, g_wl, g_bl, g_wr, g_br, g_att, g_we, g_bias, g_ea = g
+        ws, ws_bytes = _scratch("gcm_csr_gatv2_bwd", M, E, Fi, cfg.H, cfg.C, D, cfg.concat, device=x.device)
+        _call("gcm_csr_gatv2_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w_l), _hip.ptr(w_r), _hip.ptr(att),
+              _hip.ptr(w_e), _hip.ptr(edge_attr), _hip.ptr(graph.row_ptr), _hip.ptr(graph.col),
+              _hip.ptr(graph.csr_perm), _hip.ptr(col_ptr), _hip.ptr(rows), _hip.ptr(csc_perm), _hip.ptr(xl),
+              _hip.ptr(xr), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(g_x), _hip.ptr(g_wl), _hip.ptr(g_bl),
+              _hip.ptr(g_wr), _hip.ptr(g_br), _hip.ptr(g_att), _hip.ptr(g_we), _hip.ptr(g_ea), _hip.ptr(g_bias),
+              _hip.ptr(ws), ws_bytes, M, E, Fi, cfg.H, cfg.C, D, *cfg.tail())
+        return g_x, g_wl, g_bl, g_wr, g_br, g_att, g_we, g_bias, g_ea, None, None
+
+
+def csr_gatv2conv(x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr, graph, cfg):
+    """-> out [M, H*C or C]; att is viewed flat [H*C]; w_r None: lin_r is lin_l."""
+    return _CsrGATv2Conv.apply(x, w_l, b_l, w_r, b_r, att.view(-1), w_e, bias, edge_attr, graph, cfg)
+
+
+class _DenseGATv2Conv(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (only its nonzero pattern is read: no gradient), edge_attr [B,N,N,D] or None."""
+
+    @staticmethod
+    def forward(ctx, x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr, adj, cfg):
+        ops, Fi, D = _gatv2_operands(cfg, x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr)
+        x, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr = ops
+        adj = adj.contiguous()
+        _hip.on_device(adj)
+        B, N, H, C = x.shape[0], x.shape[1], cfg.H, cfg.C
+        assert adj.shape == (B, N, N) and (edge_attr is None or edge_attr.shape == (B, N, N, D))
+        dev = x.device
+        out = torch.empty(B, N, H * C if cfg.concat else C, device=dev, dtype=_f32)
+        xl = torch.empty(B, N, H * C, device=dev, dtype=_f32)
+        xr = torch.empty(B, N, H * C, device=dev, dtype=_f32) if w_r is not None else None
+        stats = torch.empty(2, B, N, H, device=dev, dtype=_f32)
+        bits = torch.empty(B, N, (N + 31) // 32, device=dev, dtype=torch.int32)
+        ws, ws_bytes = _scratch("gcm_dense_gatv2_fwd", B, N, H, C, cfg.concat, device=dev)
+        _call("gcm_dense_gatv2_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(w_l), _hip.ptr(b_l), _hip.ptr(w_r),
+              _hip.ptr(b_r), _hip.ptr(att), _hip.ptr(w_e), _hip.ptr(bias), _hip.ptr(edge_attr), _hip.ptr(out),
+              _hip.ptr(xl), _hip.ptr(xr), _hip.ptr(stats[0]), _hip.ptr(stats[1]), _hip.ptr(bits), _hip.ptr(ws),
+              ws_bytes, B, N, Fi, H, C, D, *cfg.tail())
+        ctx.save_for_backward(x, w_l, w_r, att, w_e, edge_attr, xl, xr, stats, bits)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w_l, w_r, att, w_e, edge_attr, xl, xr, stats, bits = ctx.saved_tensors
+        cfg = ctx.cfg
+        B, N, Fi = x.shape
+        D = 0 if w_e is None else w_e.shape[1]
+        g_out = _hip.kernel_ready(g_out)
+        g = _gatv2_grads(ctx, cfg, x, w_l, w_r, w_e, edge_attr)
+        g_x, g_wl, g_bl, g_wr, g_br, g_att, g_we, g_bias, g_ea = g
+        ws, ws_bytes = _scratch("gcm_dense_gatv2_bwd", B, N, Fi, cfg.H, cfg.C, D, cfg.concat, device=x.device)
+        _call("gcm_dense_gatv2_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(w_l), _hip.ptr(w_r), _hip.ptr(att),
+              _hip.ptr(w_e), _hip.ptr(edge_attr), _hip.ptr(bits), _hip.ptr(xl), _hip.ptr(xr), _hip.ptr(stats[0]),
+              _hip.ptr(stats[1]), _hip.ptr(g_x), _hip.ptr(g_wl), _hip.ptr(g_bl), _hip.ptr(g_wr), _hip.ptr(g_br),
+              _hip.ptr(g_att), _hip.ptr(g_we), _hip.ptr(g_ea), _hip.ptr(g_bias), _hip.ptr(ws), ws_bytes, B, N, Fi,
+              cfg.H, cfg.C, D, *cfg.tail())
+        return g_x, g_wl, g_bl, g_wr, g_br, g_att, g_we, g_bias, g_ea, None, None
+
+
+def dense_gatv2conv(x, adj, w_l, b_l, w_r, b_r, att, w_e, bias, edge_attr, cfg):
+    return _DenseGATv2Conv.apply(x, w_l, b_l, w_r, b_r, att.view(-1), w_e, bias, edge_attr, adj.detach(), cfg)
+
+
+# ---------------------------------------------------------------------------
 # DenseGATConv / GATConv (PyG, GAT v1; csrc/gatconv.hip)
 # ---------------------------------------------------------------------------
 class _DenseGATConv(torch.autograd.Function):

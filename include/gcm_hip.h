@@ -443,6 +443,10 @@ int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_p
  * Declared in gcm_hip_gine.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_gine.h"
 
+/* ---- GATv2Conv / DenseGATv2Conv with edge_dim (PyG; csrc/gatv2conv.hip) ----
+ * Declared in gcm_hip_gatv2.h, which is part of this header and included here (inside the extern "C" block). */
+#include "gcm_hip_gatv2.h"
+
 /* ---- ResGatedGraphConv / DenseResGatedGraphConv (PyG; csrc/resgatedconv.hip) ----
  * Declared in gcm_hip_resgated.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_resgated.h"
