@@ -42,6 +42,10 @@ _CONSTANTS.update(_abi.constants(_GINE_HEADER))
 _GATV2_HEADER = _abi.header("gcm_hip_gatv2.h")
 GATV2_PROTOTYPES = _abi.prototypes(_GATV2_HEADER)
 _CONSTANTS.update(_abi.constants(_GATV2_HEADER))
+# and the section from gcm_hip_transformer_edge.h (TransformerConv / DenseTransformerConv with edge_dim)
+_TRE_HEADER = _abi.header("gcm_hip_transformer_edge.h")
+TRE_PROTOTYPES = _abi.prototypes(_TRE_HEADER)
+_CONSTANTS.update(_abi.constants(_TRE_HEADER))
 # and the section from gcm_hip_bptt_hops.h (the GEMM-form backward of forward-hop cached chains)
 BPTT_HOPS_PROTOTYPES = _abi.prototypes(_abi.header("gcm_hip_bptt_hops.h"))
 # and the section from gcm_hip_bptt_hops_unfolded.h (that backward before the hop sum was folded into its products: the A/B)
@@ -132,6 +136,7 @@ def lib():
         bind(handle, GIN_PROTOTYPES)
         bind(handle, GINE_PROTOTYPES)
         bind(handle, GATV2_PROTOTYPES)
+        bind(handle, TRE_PROTOTYPES)
         bind(handle, BPTT_HOPS_PROTOTYPES)
         bind(handle, BPTT_HOPS_UNFOLDED_PROTOTYPES)
         bind(handle, RESGATED_PROTOTYPES)

@@ -1580,6 +1580,116 @@ def csr_transformerconv(x, w_all, b_all, w_beta, graph, heads, concat, root):
 
 
 # ---------------------------------------------------------------------------
+# TransformerConv / DenseTransformerConv with edge_dim (gcm.transformer; csrc/transformer_edge.hip).  w_e [H*C, D] is
+# lin_edge's weight; nothing per edge wider than D is formed, the forward saves u and abar [rows, H, D] beside what the
+# edge-free forward saves.
+# ---------------------------------------------------------------------------
+def _tre_operands(x, edge_attr, w_all, b_all, w_e, w_beta, heads, concat, root):
+    """Contiguous operands, checked against each other -> (operands, (Fi, H, C, D, Do))."""
+    ops = [_contig(t) for t in (x, edge_attr, w_all, b_all, w_e, w_beta)]
+    if ops[5] is not None:
+        ops[5] = ops[5].view(-1)
+    x, edge_attr, w_all, b_all, w_e, w_beta = ops
+    _hip.on_device(*ops)
+    Fi = x.shape[-1]
+    H, C, Do = _transformer_dims(w_all, heads, concat, root)
+    D = w_e.shape[1]
+    assert w_all.shape[1] == Fi and b_all.numel() == w_all.shape[0]
+    assert w_e.shape == (H * C, D) and edge_attr.shape[-1] == D
+    assert w_beta is None or w_beta.numel() == 3 * Do
+    return ops, (Fi, H, C, D, Do)
+
+
+def _tre_grads(ctx, x, edge_attr, w_all, w_e, w_beta):
+    """The outputs the backward call is to fill (None: skip): g_x, g_edge_attr, g_w_all, g_b_all, g_w_e, g_w_beta."""
+    need = ctx.needs_input_grad
+    return (torch.empty_like(x) if need[0] else None, torch.empty_like(edge_attr) if need[1] else None,
+            torch.empty_like(w_all) if need[2] else None,
+            torch.empty(w_all.shape[0], device=x.device, dtype=_f32) if need[3] else None,
+            torch.empty_like(w_e) if need[4] else None,
+            torch.empty_like(w_beta) if need[5] and w_beta is not None else None)
+
+
+class _CsrTransformerEdge(torch.autograd.Function):
+    """x [M,Fi], edge_attr [E,D] in the order of graph.edge_index."""
+
+    @staticmethod
+    def forward(ctx, x, edge_attr, w_all, b_all, w_e, w_beta, graph, heads, concat, root):
+        ops, (Fi, H, C, D, Do) = _tre_operands(x, edge_attr, w_all, b_all, w_e, w_beta, heads, concat, root)
+        x, edge_attr, w_all, b_all, w_e, w_beta = ops
+        M = x.shape[0]
+        assert M == graph.M and edge_attr.shape[0] == graph.E
+        dims = (M, graph.E, Fi, H, C, D, int(concat), int(root))
+        out = torch.empty(M, Do, device=x.device, dtype=_f32)
+        saved, saved_bytes = _scratch("gcm_csr_transformer_edge_fwd", *dims, device=x.device)
+        _call("gcm_csr_transformer_edge_fwd", _hip.ptr(x), _hip.ptr(edge_attr), _hip.ptr(graph.row_ptr),
+              _hip.ptr(graph.col), _hip.ptr(graph.csr_perm), _hip.ptr(w_all), _hip.ptr(b_all), _hip.ptr(w_e),
+              _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims, _hip.stream())
+        ctx.save_for_backward(x, edge_attr, w_all, w_e, w_beta, saved)
+        ctx.graph, ctx.dims = graph, dims
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, edge_attr, w_all, w_e, w_beta, saved = ctx.saved_tensors
+        graph = ctx.graph
+        g_out = _hip.kernel_ready(g_out)
+        col_ptr, rows, perm = _csc_or_none(graph, graph.E > 0)
+        g_x, g_ea, g_w, g_b, g_we, g_beta = _tre_grads(ctx, x, edge_attr, w_all, w_e, w_beta)
+        ws, ws_bytes = _scratch("gcm_csr_transformer_edge_bwd", *ctx.dims, device=x.device)
+        _call("gcm_csr_transformer_edge_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(edge_attr),
+              _hip.ptr(graph.row_ptr), _hip.ptr(graph.col), _hip.ptr(graph.csr_perm), _hip.ptr(col_ptr),
+              _hip.ptr(rows), _hip.ptr(perm), _hip.ptr(w_all), _hip.ptr(w_e), _hip.ptr(w_beta), _hip.ptr(saved),
+              _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b), _hip.ptr(g_we), _hip.ptr(g_beta), _hip.ptr(g_ea),
+              _hip.ptr(ws), ws_bytes, *ctx.dims, _hip.stream())
+        return g_x, g_ea, g_w, g_b, g_we, g_beta, None, None, None, None
+
+
+def csr_transformer_edge(x, edge_attr, w_all, b_all, w_e, w_beta, graph, heads, concat, root):
+    """-> out [M, H*C or C]; w_all / b_all / w_beta as csr_transformerconv's, w_e [H*C, D]."""
+    return _CsrTransformerEdge.apply(x, edge_attr, w_all, b_all, w_e, w_beta, graph, heads, concat, root)
+
+
+class _DenseTransformerEdge(torch.autograd.Function):
+    """x [B,N,Fi], adj [B,N,N] (only its nonzero pattern is read: no gradient), edge_attr [B,N,N,D]."""
+
+    @staticmethod
+    def forward(ctx, x, edge_attr, w_all, b_all, w_e, w_beta, adj, heads, concat, root, add_loop):
+        ops, (Fi, H, C, D, Do) = _tre_operands(x, edge_attr, w_all, b_all, w_e, w_beta, heads, concat, root)
+        x, edge_attr, w_all, b_all, w_e, w_beta = ops
+        adj = adj.contiguous()
+        _hip.on_device(adj)
+        B, N = x.shape[0], x.shape[1]
+        assert adj.shape == (B, N, N) and edge_attr.shape == (B, N, N, D)
+        dims = (B, N, Fi, H, C, D, int(concat), int(root))
+        out = torch.empty(B, N, Do, device=x.device, dtype=_f32)
+        saved, saved_bytes = _scratch("gcm_dense_transformer_edge_fwd", *dims, device=x.device)
+        _call("gcm_dense_transformer_edge_fwd", _hip.ptr(x), _hip.ptr(adj), _hip.ptr(edge_attr), _hip.ptr(w_all),
+              _hip.ptr(b_all), _hip.ptr(w_e), _hip.ptr(w_beta), _hip.ptr(out), _hip.ptr(saved), saved_bytes, *dims,
+              int(add_loop), _hip.stream())
+        ctx.save_for_backward(x, edge_attr, w_all, w_e, w_beta, saved)
+        ctx.dims = dims
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, edge_attr, w_all, w_e, w_beta, saved = ctx.saved_tensors
+        g_out = _hip.kernel_ready(g_out)
+        g_x, g_ea, g_w, g_b, g_we, g_beta = _tre_grads(ctx, x, edge_attr, w_all, w_e, w_beta)
+        ws, ws_bytes = _scratch("gcm_dense_transformer_edge_bwd", *ctx.dims, device=x.device)
+        _call("gcm_dense_transformer_edge_bwd", _hip.ptr(g_out), _hip.ptr(x), _hip.ptr(edge_attr), _hip.ptr(w_all),
+              _hip.ptr(w_e), _hip.ptr(w_beta), _hip.ptr(saved), _hip.ptr(g_x), _hip.ptr(g_w), _hip.ptr(g_b),
+              _hip.ptr(g_we), _hip.ptr(g_beta), _hip.ptr(g_ea), _hip.ptr(ws), ws_bytes, *ctx.dims, _hip.stream())
+        return g_x, g_ea, g_w, g_b, g_we, g_beta, None, None, None, None, None
+
+
+def dense_transformer_edge(x, adj, edge_attr, w_all, b_all, w_e, w_beta, heads, concat, root, add_loop):
+    """-> out [B,N, H*C or C]; g_edge_attr is written whole (zero where there is no term)."""
+    return _DenseTransformerEdge.apply(x, edge_attr, w_all, b_all, w_e, w_beta, adj.detach(), heads, concat, root,
+                                       add_loop)
+
+
+# ---------------------------------------------------------------------------
 # DenseResGatedGraphConv / ResGatedGraphConv (PyG; csrc/resgatedconv.hip)
 # ---------------------------------------------------------------------------
 def _resgated_dims(w_all, root):

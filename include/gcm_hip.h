@@ -447,6 +447,11 @@ int gcm_csr_gatconv_bwd(const float* g_out, const float* x, const int64_t* row_p
  * Declared in gcm_hip_gatv2.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_gatv2.h"
 
+/* ---- TransformerConv / DenseTransformerConv with edge_dim (PyG; csrc/transformer_edge.hip) ----
+ * Declared in gcm_hip_transformer_edge.h, which is part of this header and included here (inside the extern "C"
+ * block). */
+#include "gcm_hip_transformer_edge.h"
+
 /* ---- ResGatedGraphConv / DenseResGatedGraphConv (PyG; csrc/resgatedconv.hip) ----
  * Declared in gcm_hip_resgated.h, which is part of this header and included here (inside the extern "C" block). */
 #include "gcm_hip_resgated.h"
