@@ -5,9 +5,8 @@
 // live-row kernel (rows_step.hip: it re-aggregates every live row from the adjacency at every step: cur^2 F
 // work per graph with DenseEdge, five barriers per 16 rows).
 //
-// In a chain that started from EMPTY graphs on a donated state and has made fewer than N steps (nothing has
-// overflowed; every graph holds exactly `cur` nodes, and the host knows cur), a column write is a RANK-1
-// correction of what the chain already knows:
+// In a chain that started from EMPTY graphs (donated or functional state; every graph holds min(steps made, N)
+// nodes, and the host knows the step count), a column write is a RANK-1 correction of what the chain already knows:
 //
 //     agg1[j] = sum_k adj[j,k] x[k]      gains   + x[cur]    for the rows j the selectors give the entry (j, cur)
 //     root[j] = W_root1 x[j] + b1        is final once node j is written
@@ -17,9 +16,23 @@
 // column sum of the node matrix), the rank-1 update of the touched rows, ONE [rows x F] . [F x H1] product on the
 // fp32 matrix cores for the live rows (32 rows per wave: v_mfma_f32_32x32x2_f32 with both operands straight from
 // global memory into the registers that feed it - lane (row, half) owns F/2 contiguous k of its row, the same k
-// of W_rel1's row `col` as the B operand), the activation, agg2, and layer 2 on row cur.  Exact: the same sums as
-// the reference's adj @ x (ones and zeros), accumulated in ascending source order.  cur^2 F per graph-step
+// of W_rel1's row `col` as the B operand), the activation, agg2, and layer 2 on row cur.  cur^2 F per graph-step
 // becomes cur F (update) + 2 cur F H1 (product).
+//
+// Past N steps the caches are rings (slot of a node = its chain index mod N): a full graph drops its oldest node at
+// every step, and the rows that held it as a source get the opposite correction, agg1[j] -= x[dropped].
+//
+// Precision.  These are NOT the reference's sums: the reference adds a row's sources afresh at every step, here a
+// row's aggregate is one sum at the row's creation and a correction per step after that.  In fp32 that goes wrong as
+// soon as one observation is large: an aggregate that holds it has rounded away ~eps |outlier| of its small terms, the
+// subtraction then removes the outlier exactly and leaves that error in the row until the row is dropped itself, up to
+// N steps later (tests/test_ring_conditioning_cpu.py: 300 x the reference's own fp32 error with one observation of
+// 2^12).  So the aggregate cache is FLOAT64: the new row's masked column sum (per-thread partials, the LDS image, the
+// sum over the row groups), the cache plane and both corrections.  Every addition of fp32 values then rounds at
+// 2^-53 of the running sum, not 2^-24: what add-then-subtract leaves behind is ~1e-16 |outlier| per step, and the
+// order of the additions no longer shows in the fp32 result.  A value is rounded to fp32 once, where it enters the
+// layer-1 product and the record (which keeps its fp32 layout: k_bptt_rows is unchanged) - the correctly rounded
+// aggregate, closer to the exact sum than the reference's own fp32 accumulation.
 //
 // Which rows: the host folds the selector chain and cur into two 128-bit masks -
 //   srow: the sources of row cur (bit cur = a self edge),  scol: the older rows that gain the source cur.
@@ -60,6 +73,9 @@ __device__ __forceinline__ int mrank(const RowMask& m, int j) {
   if (j < 64) return __popcll(m.lo & ((1ull << j) - 1ull));
   return __popcll(m.lo) + __popcll(m.hi & ((1ull << (j - 64)) - 1ull));
 }
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+// v + the value of lane ^ 32, in float64
+__device__ __forceinline__ double xor32_add64(double v) { return v + __shfl_xor(v, 32, 64); }
 // LDS exchange between the waves of the workgroup: waits for this wave's LDS operations only - __syncthreads() also
 // drains the wave's global loads and STORES (vmcnt(0)), which here would put every barrier behind the record's stores
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -76,7 +92,7 @@ template <int FK, int HK, int O2T, bool FUNC>
 __global__ __launch_bounds__(256) void k_step_colcache(
     const float* __restrict__ obs, const float* nodes_in, const float* adj_in, const int64_t* count_in, float* nodes,
     float* adj, int64_t* count, const RowMask ssrc, const int self, const RowMask scol, const RowMask sdrop,
-    const int cur, const int rot, const int steady, const Gnn2 P, float* __restrict__ cA, float* __restrict__ cR,
+    const int cur, const int rot, const int steady, const Gnn2 P, double* __restrict__ cA, float* __restrict__ cR,
     float* __restrict__ saved, const SavedLayout lay, uint32_t* __restrict__ flags, const int N, const int H2,
     const Edits E, const int Bn) {
   if (FUNC && (int)blockIdx.x >= Bn) {
@@ -95,7 +111,7 @@ __global__ __launch_bounds__(256) void k_step_colcache(
   constexpr int PS = FK + 4;       // stride of the partial-sum image
   constexpr int SPLIT = 64 / FK;   // lanes per feature in the row-group sum (2 or 1)
   constexpr int GP = RG / SPLIT;   // row groups per lane there (16)
-  __shared__ __attribute__((aligned(16))) float sPart[RG * PS];
+  __shared__ __attribute__((aligned(16))) double sPart[RG * PS];
   __shared__ __attribute__((aligned(16))) float sAggc[FK];
   __shared__ float sRcur[HK];
   __shared__ __attribute__((aligned(16))) float sV[2 * HK];
@@ -108,7 +124,7 @@ __global__ __launch_bounds__(256) void k_step_colcache(
   const float* ng_in = nodes_in + gb * N * FK;   // the state as it comes in (FUNC: never written)
   float* ng = nodes + gb * N * FK;               // donated: the same matrix, advanced in place
   float* ag = adj + gb * N * N;
-  float* cAg = cA + gb * N * FK;
+  double* cAg = cA + gb * N * FK;
   float* cRg = cR + gb * N * HK;
   const bool rec = lay.total != 0;
   const int rw = lay.rw;
@@ -168,12 +184,13 @@ __global__ __launch_bounds__(256) void k_step_colcache(
   // the B operand: W_rel1[col][k], col = 32 ct + li, the same k; root[slot][col] of the rows the accumulators hold
   const int r = 32 * wave + li;
   const int rc = r < N ? r : N - 1;
-  f32x4 ca[KQ], wb[CT][KQ], crq[CT][4];
+  f64x2 ca[2 * KQ];
+  f32x4 wb[CT][KQ], crq[CT][4];
   const int NQ = N >> 2;   // the root cache is kept in quads of rows: cR[b][slot / 4][col][slot % 4] (one 16-byte load
                            // per four accumulator rows of a lane)
   if (tile_on) {
 #pragma unroll
-    for (int q = 0; q < KQ; ++q) ca[q] = *reinterpret_cast<const f32x4*>(cAg + rc * FK + lh * KH + 4 * q);
+    for (int q = 0; q < 2 * KQ; ++q) ca[q] = *reinterpret_cast<const f64x2*>(cAg + rc * FK + lh * KH + 2 * q);
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -225,7 +242,7 @@ __global__ __launch_bounds__(256) void k_step_colcache(
   auto new_row_sum = [&](auto ringc) {
     constexpr bool RING = decltype(ringc)::value;   // rot != 0: slot = (row + rot) mod N; else slot = row and the
                                                     // mask word of a pass is a compile-time choice of a scalar
-    f32x4 part = {0.f, 0.f, 0.f, 0.f};
+    f64x2 part0 = {0., 0.}, part1 = {0., 0.};   // float64: see the file header
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
       if (RG * i >= n_slots) continue;   // uniform
@@ -245,11 +262,15 @@ __global__ __launch_bounds__(256) void k_step_colcache(
         pos = (unsigned)sbase(w) + (unsigned)__popc(word & ((1u << bit) - 1u));
       }
       const f32x4 v = is_cur ? obq : xr[i];
-      if (stored || (is_cur && self != 0)) part += v;
+      if (stored || (is_cur && self != 0)) {
+        part0 += f64x2{(double)v.x, (double)v.y};
+        part1 += f64x2{(double)v.z, (double)v.w};
+      }
       if (rec && (stored || is_cur))
         *reinterpret_cast<f32x4*>(sv_rows + (is_cur ? 0u : pos) * (unsigned)rw + HK + FK + 4 * c4) = v;
     }
-    *reinterpret_cast<f32x4*>(sPart + rg * PS + 4 * c4) = part;
+    *reinterpret_cast<f64x2*>(sPart + rg * PS + 4 * c4) = part0;
+    *reinterpret_cast<f64x2*>(sPart + rg * PS + 4 * c4 + 2) = part1;
   };
   if (rot) new_row_sum(std::true_type{});
   else new_row_sum(std::false_type{});
@@ -290,17 +311,17 @@ __global__ __launch_bounds__(256) void k_step_colcache(
   }
   if (wave == 2) {   // the row groups' partial sums -> agg1[cur]: lane (feature, part) takes GP groups
     const int f = lane % FK, part = lane / FK;
-    float v[GP];
+    double v[GP];
 #pragma unroll
     for (int g = 0; g < GP; ++g) v[g] = sPart[(part * GP + g) * PS + f];
-    float s = 0.f;
+    double s = 0.;
 #pragma unroll
     for (int g = 0; g < GP; ++g) s += v[g];
-    if (SPLIT == 2) s = gcm_xor32_add(s);
+    if (SPLIT == 2) s = xor32_add64(s);
     if (part == 0) {
-      sAggc[f] = s;
       cAg[cur * FK + f] = s;
-      if (rec) sv_rows[HK + f] = s;
+      sAggc[f] = (float)s;   // rounded once, where the product and the record take it
+      if (rec) sv_rows[HK + f] = (float)s;
     }
   }
   lds_barrier();   // #2
@@ -321,11 +342,19 @@ __global__ __launch_bounds__(256) void k_step_colcache(
       float a[KH];
 #pragma unroll
       for (int q = 0; q < KQ; ++q) {
-        f32x4 v = ca[q];
+        f64x2 d0 = ca[2 * q], d1 = ca[2 * q + 1];
         const f32x4 xq = xa[q], xd = xo[q];
-        if (steady) v -= f32x4{drp ? xd.x : 0.f, drp ? xd.y : 0.f, drp ? xd.z : 0.f, drp ? xd.w : 0.f};   // (uniform)
-        v += f32x4{upd ? xq.x : 0.f, upd ? xq.y : 0.f, upd ? xq.z : 0.f, upd ? xq.w : 0.f};
-        if (upd || drp) *reinterpret_cast<f32x4*>(cAg + r * FK + lh * KH + 4 * q) = v;
+        if (steady) {   // (uniform)
+          d0 -= f64x2{drp ? (double)xd.x : 0., drp ? (double)xd.y : 0.};
+          d1 -= f64x2{drp ? (double)xd.z : 0., drp ? (double)xd.w : 0.};
+        }
+        d0 += f64x2{upd ? (double)xq.x : 0., upd ? (double)xq.y : 0.};
+        d1 += f64x2{upd ? (double)xq.z : 0., upd ? (double)xq.w : 0.};
+        if (upd || drp) {
+          *reinterpret_cast<f64x2*>(cAg + r * FK + lh * KH + 4 * q) = d0;
+          *reinterpret_cast<f64x2*>(cAg + r * FK + lh * KH + 4 * q + 2) = d1;
+        }
+        f32x4 v = {(float)d0.x, (float)d0.y, (float)d1.x, (float)d1.y};   // fp32 from here: the product, the record
         if (li == cur_bit) v = *reinterpret_cast<const f32x4*>(sAggc + lh * KH + 4 * q);
         if (rec && lrow) *reinterpret_cast<f32x4*>(rdst + 4 * q) = v;
         a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
@@ -507,7 +536,7 @@ template <int O2T, bool FUNC>
 __global__ __launch_bounds__(512) void k_step_colcache8(
     const float* __restrict__ obs, const float* nodes_in, const float* adj_in, const int64_t* count_in, float* nodes,
     float* adj, int64_t* count, const RowMask ssrc, const int self, const RowMask scol, const RowMask sdrop,
-    const int cur, const int rot, const int steady, const Gnn2 P, float* __restrict__ cA, float* __restrict__ cR,
+    const int cur, const int rot, const int steady, const Gnn2 P, double* __restrict__ cA, float* __restrict__ cR,
     float* __restrict__ saved, const SavedLayout lay, uint32_t* __restrict__ flags, const int N, const int H2,
     const Edits E, const int Bn) {
   constexpr int FK = 32, HK = 32;
@@ -522,7 +551,7 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
     return;
   }
   constexpr int C4 = 8, RG = 64, XP = 2, PS = FK + 4;
-  __shared__ __attribute__((aligned(16))) float sPart[RG * PS];
+  __shared__ __attribute__((aligned(16))) double sPart[RG * PS];
   __shared__ __attribute__((aligned(16))) float sAggc[FK];
   __shared__ float sRcur[HK];
   __shared__ __attribute__((aligned(16))) float sV[2 * HK];
@@ -535,7 +564,7 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
   const float* ng_in = nodes_in + gb * N * FK;
   float* ng = nodes + gb * N * FK;
   float* ag = adj + gb * N * N;
-  float* cAg = cA + gb * N * FK;
+  double* cAg = cA + gb * N * FK;
   float* cRg = cR + gb * N * HK;
   const bool rec = lay.total != 0;
   const int rw = lay.rw;
@@ -586,10 +615,11 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
   const int r = 16 * wave + m;
   const int rc = r < N ? r : N - 1;
   const int NQ = N >> 2;
-  f32x4 ca[2], wb[2][2], crq[2];
+  f64x2 ca[4];
+  f32x4 wb[2][2], crq[2];
   if (tile_on) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) ca[q] = *reinterpret_cast<const f32x4*>(cAg + rc * FK + 8 * g + 4 * q);
+    for (int q = 0; q < 4; ++q) ca[q] = *reinterpret_cast<const f64x2*>(cAg + rc * FK + 8 * g + 2 * q);
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -630,7 +660,7 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
   // ---- the new row's aggregate ----------------------------------------------------------------------------------------
   auto new_row_sum = [&](auto ringc) {
     constexpr bool RING = decltype(ringc)::value;
-    f32x4 part = {0.f, 0.f, 0.f, 0.f};
+    f64x2 part0 = {0., 0.}, part1 = {0., 0.};   // float64: see the file header
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
       if (RG * i >= n_slots) continue;   // uniform
@@ -650,11 +680,15 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
         pos = (unsigned)sbase(w) + (unsigned)__popc(word & ((1u << bit) - 1u));
       }
       const f32x4 v = is_cur ? obq : xr[i];
-      if (stored || (is_cur && self != 0)) part += v;
+      if (stored || (is_cur && self != 0)) {
+        part0 += f64x2{(double)v.x, (double)v.y};
+        part1 += f64x2{(double)v.z, (double)v.w};
+      }
       if (rec && (stored || is_cur))
         *reinterpret_cast<f32x4*>(sv_rows + (is_cur ? 0u : pos) * (unsigned)rw + HK + FK + 4 * c4) = v;
     }
-    *reinterpret_cast<f32x4*>(sPart + rg * PS + 4 * c4) = part;
+    *reinterpret_cast<f64x2*>(sPart + rg * PS + 4 * c4) = part0;
+    *reinterpret_cast<f64x2*>(sPart + rg * PS + 4 * c4 + 2) = part1;
   };
   if (rot) new_row_sum(std::true_type{});
   else new_row_sum(std::false_type{});
@@ -691,17 +725,17 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
   }
   if (wave == 6) {   // 64 row groups -> agg1[cur]: lane (feature, half) takes 32 groups
     const int f = lane & 31, part = lane >> 5;
-    float v[32];
+    double v[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) v[k] = sPart[(part * 32 + k) * PS + f];
-    float s0 = 0.f;
+    double s0 = 0.;
 #pragma unroll
     for (int k = 0; k < 32; ++k) s0 += v[k];
-    s0 = gcm_xor32_add(s0);
+    s0 = xor32_add64(s0);
     if (part == 0) {
-      sAggc[f] = s0;
       cAg[cur * FK + f] = s0;
-      if (rec) sv_rows[HK + f] = s0;
+      sAggc[f] = (float)s0;
+      if (rec) sv_rows[HK + f] = (float)s0;
     }
   }
   lds_barrier();   // #2
@@ -716,11 +750,19 @@ __global__ __launch_bounds__(512) void k_step_colcache8(
     float a[8];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      f32x4 v = ca[q];
+      f64x2 d0 = ca[2 * q], d1 = ca[2 * q + 1];
       const f32x4 xq = xa[q], xd = xo[q];
-      if (steady) v -= f32x4{drp ? xd.x : 0.f, drp ? xd.y : 0.f, drp ? xd.z : 0.f, drp ? xd.w : 0.f};
-      v += f32x4{upd ? xq.x : 0.f, upd ? xq.y : 0.f, upd ? xq.z : 0.f, upd ? xq.w : 0.f};
-      if (upd || drp) *reinterpret_cast<f32x4*>(cAg + r * FK + 8 * g + 4 * q) = v;
+      if (steady) {
+        d0 -= f64x2{drp ? (double)xd.x : 0., drp ? (double)xd.y : 0.};
+        d1 -= f64x2{drp ? (double)xd.z : 0., drp ? (double)xd.w : 0.};
+      }
+      d0 += f64x2{upd ? (double)xq.x : 0., upd ? (double)xq.y : 0.};
+      d1 += f64x2{upd ? (double)xq.z : 0., upd ? (double)xq.w : 0.};
+      if (upd || drp) {
+        *reinterpret_cast<f64x2*>(cAg + r * FK + 8 * g + 4 * q) = d0;
+        *reinterpret_cast<f64x2*>(cAg + r * FK + 8 * g + 4 * q + 2) = d1;
+      }
+      f32x4 v = {(float)d0.x, (float)d0.y, (float)d1.x, (float)d1.y};
       if (m == cur_bit) v = *reinterpret_cast<const f32x4*>(sAggc + 8 * g + 4 * q);
       if (rec && lrow) *reinterpret_cast<f32x4*>(rdst + 4 * q) = v;
       a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
@@ -924,7 +966,7 @@ extern "C" int gcm_dense_rows_colcache_supported(const gcm_selector_desc* select
 
 static int colcache_launch(const float* obs, const float* nodes_in, const float* adj_in, const int64_t* count_in,
                            float* nodes_out, float* adj_out, int64_t* count_out, const gcm_selector_desc* selectors,
-                           int n_selectors, const float* params, int has_bias, int act1, int act2, float* cache_agg1,
+                           int n_selectors, const float* params, int has_bias, int act1, int act2, double* cache_agg1,
                            float* cache_root, float* saved, int record, int cur_host, uint32_t* flags, int B, int N,
                            int F, int H1, int H2, gcm_stream_t stream) {
   GCM_REQUIRE(obs && nodes_in && adj_in && count_in && nodes_out && adj_out && count_out && params && cache_agg1 &&
@@ -977,7 +1019,7 @@ static int colcache_launch(const float* obs, const float* nodes_in, const float*
 
 extern "C" int gcm_dense_rows_step_colcache(const float* obs, float* nodes, float* adj, int64_t* count,
                                             const gcm_selector_desc* selectors, int n_selectors, const float* params,
-                                            int has_bias, int act1, int act2, float* cache_agg1, float* cache_root,
+                                            int has_bias, int act1, int act2, double* cache_agg1, float* cache_root,
                                             float* saved, int record, int cur_host, uint32_t* flags, int B, int N,
                                             int F, int H1, int H2, gcm_stream_t stream) {
   return colcache_launch(obs, nodes, adj, count, nodes, adj, count, selectors, n_selectors, params, has_bias, act1, act2,
@@ -988,7 +1030,7 @@ extern "C" int gcm_dense_rows_step_colcache_functional(const float* obs, const f
                                                        const int64_t* count_in, float* nodes_out, float* adj_out,
                                                        int64_t* count_out, const gcm_selector_desc* selectors,
                                                        int n_selectors, const float* params, int has_bias, int act1,
-                                                       int act2, float* cache_agg1, float* cache_root, float* saved,
+                                                       int act2, double* cache_agg1, float* cache_root, float* saved,
                                                        int record, int cur_host, uint32_t* flags, int B, int N, int F,
                                                        int H1, int H2, gcm_stream_t stream) {
   GCM_REQUIRE(nodes_out != nodes_in && adj_out != adj_in && count_out != count_in);

@@ -674,15 +674,15 @@ struct RowsFast {
   // the adjacency (abits, kept by the cached steps)
   bool ring_ok = false;
   // ... or (round 6) the chain's selectors also write COLUMN cur - DenseEdge, "backward" / "both" hops - on a donated
-  // state from empty graphs: gcm_dense_rows_step_colcache (rank-1 updates of the chain's agg1 cache, one MFMA product of
-  // the live rows), the general live-row record; past N steps the general kernel
+  // or functional state from empty graphs: gcm_dense_rows_step_colcache (rank-1 updates of the chain's float64 agg1 cache, one MFMA
+  // product of the live rows), the general live-row record; past N steps its ring form
   bool col_ok = false;
   int64_t cached_steps = 0, chain_steps = 0, rolled_steps = 0, col_steps = 0;
   at::Tensor cH, cA, cX, wimg, abits;
   // the weight image the fused head launch (pack_params_head) made beside a packed vector, and that vector: taken by
   // the chain's first cached step iff it is armed with that very tensor
   at::Tensor head_img, head_img_of;
-  at::Tensor kA, kR;   // the column-write chain's caches: agg1 [B,N,F], root [B,N,H1]
+  at::Tensor kA, kR;   // the column-write chain's caches: agg1 [B,N,F] in float64, root [B,N,H1]
   at::Tensor rH, rA, rX;   // the ring caches of the steady-state steps (copies: the first N records keep reading cH / cA / cX)
   std::shared_ptr<DxChain> dxc;
   std::shared_ptr<DxGateNode> dx_gate;
@@ -895,7 +895,7 @@ struct RowsFast {
     const int N = cfg->N, F = cfg->F, H1 = cfg->H1, H2 = cfg->H2;
     const bool need_bwd = node != nullptr;
     if (cached_steps == 0) {   // (uninitialised: a row is read only after the step that wrote it)
-      kA = at::empty({B, N, F}, obs.options());
+      kA = at::empty({B, N, F}, obs.options().dtype(at::kDouble));
       kR = at::empty({B, N, H1}, obs.options());
     }
     size_t lay[8];
@@ -907,7 +907,7 @@ struct RowsFast {
       check(gcm_dense_rows_step_colcache(obs.data_ptr<float>(), nodes_in.data_ptr<float>(), adj_in.data_ptr<float>(),
                                          count_in.data_ptr<int64_t>(), cfg->descs.data(), (int)cfg->descs.size(),
                                          packed.data_ptr<float>(), cfg->has_bias, cfg->act1, cfg->act2,
-                                         kA.data_ptr<float>(), kR.data_ptr<float>(), buf.data_ptr<float>(),
+                                         kA.data_ptr<double>(), kR.data_ptr<float>(), buf.data_ptr<float>(),
                                          need_bwd ? 1 : 0, (int)cached_steps,
                                          reinterpret_cast<uint32_t*>(flags.data_ptr()), (int)B, N, F, H1, H2, stream),
             "gcm_dense_rows_step_colcache");
@@ -921,7 +921,7 @@ struct RowsFast {
                 obs.data_ptr<float>(), nodes_in.data_ptr<float>(), adj_in.data_ptr<float>(),
                 count_in.data_ptr<int64_t>(), nodes_out.data_ptr<float>(), adj_out.data_ptr<float>(),
                 count_out.data_ptr<int64_t>(), cfg->descs.data(), (int)cfg->descs.size(), packed.data_ptr<float>(),
-                cfg->has_bias, cfg->act1, cfg->act2, kA.data_ptr<float>(), kR.data_ptr<float>(), buf.data_ptr<float>(),
+                cfg->has_bias, cfg->act1, cfg->act2, kA.data_ptr<double>(), kR.data_ptr<float>(), buf.data_ptr<float>(),
                 need_bwd ? 1 : 0, (int)cached_steps, reinterpret_cast<uint32_t*>(flags.data_ptr()), (int)B, N, F, H1,
                 H2, stream),
             "gcm_dense_rows_step_colcache_functional");

@@ -60,12 +60,13 @@ int gcm_version(void);
  * buffer changes, or an entry point is removed (6: round 5 did the first two - the weight image of
  * gcm_dense_rows_cached_weight_image grew from 16 384 to gcm_dense_rows_cached_weight_image_floats() = 36 864 floats,
  * and gcm_edge_distance_step_cached / gcm_learned_step_cached(_functional) / gcm_learned_bptt_cached gained pointer
- * arguments mid-signature; 7: gcm_learned_step_bwd, the single-step LearnedEdge backward, was retired).  A binding
+ * arguments mid-signature; 7: gcm_learned_step_bwd, the single-step LearnedEdge backward, was retired; 8: cache_agg1 of
+ * gcm_dense_rows_step_colcache(_functional) became a float64 plane - double*, twice the bytes).  A binding
  * compares gcm_abi_version() with the GCM_ABI_VERSION it was written against before any other call (gcm/_hip.py
  * does; INTEGRATION.md shows the stub) - stale ctypes prototypes would otherwise shift pointers silently.
  * The Python binding (gcm/_abi.py) is derived from the text of this file: a declaration, constant or struct member
  * written in a form that reader cannot map to ctypes fails at import, naming it. */
-#define GCM_ABI_VERSION 7
+#define GCM_ABI_VERSION 8
 int gcm_abi_version(void);
 const char* gcm_status_string(int code);
 
@@ -875,15 +876,22 @@ int gcm_dense_rows_step_cached_roll(const float* obs, float* nodes, const gcm_se
                                     gcm_stream_t stream);
 /* The cached step for selector chains that also write COLUMN cur of the adjacency (round 6): DenseEdge
  * (edge_selectors/dense.py:16-21) and TemporalBackedge with direction "backward" / "both"
- * (edge_selectors/temporal.py:82-87) - alone or chained with forward hops.  Same preconditions as
- * gcm_dense_rows_step_cached (a chain from EMPTY graphs on a donated state, fewer than N steps made), plus cur_host >= 0
- * is required (every graph of such a chain holds cur_host nodes).  A column write is a rank-1 correction of the older
- * rows' layer-1 aggregate (agg1[j] += x[cur]), so the chain keeps cache_agg1 [B,N,F] (agg1 of every node) and
- * cache_root [B,N/4,H1,4] (W_root1 x[j] + b1 in quads of rows, final once written; chain-internal layout) - both
- * uninitialised at the chain's head - and a step is
+ * (edge_selectors/temporal.py:82-87) - alone or chained with forward hops.  A linear chain from EMPTY graphs;
+ * cur_host >= 0 = the number of steps the chain has made (every graph of such a chain holds min(cur_host, N) nodes).
+ * A column write is a rank-1 correction of the older rows' layer-1 aggregate (agg1[j] += x[cur]), so the chain keeps
+ * cache_agg1 [B,N,F] (agg1 of every node, FLOAT64) and cache_root [B,N/4,H1,4] (W_root1 x[j] + b1 in quads of rows,
+ * final once written; chain-internal layout) - both uninitialised at the chain's head - and a step is
  * the masked column sum for the new row, the rank-1 update, ONE [rows x F] . [F x H1] product of the live rows on the
  * fp32 matrix cores and layer 2 on row cur: cur F + 2 cur F H1 flops per graph where the general live-row kernel
- * re-aggregates cur^2 F.  The state (nodes, adj, count) is advanced IN PLACE; a graph whose count differs from cur_host
+ * re-aggregates cur^2 F.
+ * cur_host >= N is the RING form: the graphs are full, every step drops the oldest node, the caches are rings (slot of
+ * a node = its chain index mod N) and the rows that held the dropped node as a source get the opposite correction
+ * (agg1[j] -= x[dropped]).  These are not the reference's sums - it adds every row's sources afresh at each step -
+ * which is why cache_agg1, the new row's column sum and both corrections are float64: an aggregate is rounded to fp32
+ * once, where it enters the product and the record, so a large observation that passes through a row's aggregate
+ * leaves no rounding residue behind when it is subtracted again.  (Up to ABI 7 cache_agg1 was an fp32 plane of the
+ * same shape: a caller must now hand in B N F doubles.)
+ * The state (nodes, adj, count) is advanced IN PLACE; a graph whose count differs from min(cur_host, N)
  * is left untouched and raises GCM_FLAG_BAD_COUNT.  saved: the GENERAL live-row record (gcm_dense_rows_layout; mx [B,H2]
  * at 0 - always written; the rest with record != 0), read by gcm_dense_rows_bptt.  F, H1 in {32, 64}, H2 <= 64,
  * N <= 128, has_bias without fold bits; _supported also returns 0 for chains that never write a column (they have
@@ -897,12 +905,12 @@ int gcm_dense_rows_colcache_supported(const gcm_selector_desc* selectors, int n_
 int gcm_dense_rows_step_colcache_functional(const float* obs, const float* nodes_in, const float* adj_in,
                                             const int64_t* count_in, float* nodes_out, float* adj_out,
                                             int64_t* count_out, const gcm_selector_desc* selectors, int n_selectors,
-                                            const float* params, int has_bias, int act1, int act2, float* cache_agg1,
+                                            const float* params, int has_bias, int act1, int act2, double* cache_agg1,
                                             float* cache_root, float* saved, int record, int cur_host, uint32_t* flags,
                                             int B, int N, int F, int H1, int H2, gcm_stream_t stream);
 int gcm_dense_rows_step_colcache(const float* obs, float* nodes, float* adj, int64_t* count,
                                  const gcm_selector_desc* selectors, int n_selectors, const float* params,
-                                 int has_bias, int act1, int act2, float* cache_agg1, float* cache_root, float* saved,
+                                 int has_bias, int act1, int act2, double* cache_agg1, float* cache_root, float* saved,
                                  int record, int cur_host, uint32_t* flags, int B, int N, int F, int H1, int H2,
                                  gcm_stream_t stream);
 int gcm_edge_distance_step_cached_supported(int n_cur_rows, int B, int N, int F, int H1, int H2);

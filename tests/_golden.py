@@ -143,3 +143,17 @@ def fp64_rollout_bounds(ref, obs, hidden, weight, sel_factory, graph_size, facto
         bounds[k] = (p64.grad, max(factor * err, floor * scale))
     err_o = float((out32.detach().double() - out64.detach()).abs().max())
     return out32.detach(), hid32, bounds, (out64.detach(), max(2e-6, factor * err_o))
+
+
+def fp64_regime_bounds(ref, obs, hidden, weight, sel_factory, graph_size, quiet, factor=3.0, floor=5e-7):
+    """fp64_rollout_bounds with the beliefs' bound taken over one regime of the rollout: quiet [T] (bool) marks the
+    steps it is taken over, out_atol = max(2e-6, factor x max over those steps of |reference-fp32 - fp64|).  One maximum over
+    all steps lets a large error in a few steps hide under the bound that other, ill-conditioned steps set; the
+    gradient bounds keep fp64_rollout_bounds' rule - the caller makes them sensitive to the regime by giving `weight`
+    zeros on the other steps.  -> (out32, final hidden32, {param name: (g64, atol)}, (out64, out_atol))."""
+    quiet = torch.as_tensor(quiet, dtype=torch.bool)
+    assert quiet.shape == (obs.shape[0],) and bool(quiet.any())
+    out32, hid32, bounds, (out64, _) = fp64_rollout_bounds(ref, obs, hidden, weight, sel_factory, graph_size,
+                                                           factor=factor, floor=floor)
+    err_q = float((out32.double() - out64)[quiet].abs().max())
+    return out32, hid32, bounds, (out64, max(2e-6, factor * err_q))

@@ -124,7 +124,7 @@ def test_header_section_and_library():
     assert "gcm_edge_knn_supported" not in _hip.PROTOTYPES
     assert len(_hip.PROTOTYPES) == 150                                 # no prototype of gcm_hip.h itself changed
     lib = _hip.lib()
-    assert lib.gcm_abi_version() == 7 == _hip.ABI_VERSION            # the section is additive
+    assert lib.gcm_abi_version() == 8 == _hip.ABI_VERSION            # the section is additive
     fn = lib.gcm_edge_knn_supported
     assert (fn.restype, fn.argtypes) == _hip.KNN_PROTOTYPES["gcm_edge_knn_supported"]
     L2, COS, EUC = _hip.DIST_L2_PERGRAPH, _hip.DIST_COSINE_SIM, _hip.DIST_EUCLID_CROSSBATCH

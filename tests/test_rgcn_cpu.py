@@ -164,7 +164,7 @@ def test_library_exports_every_symbol_of_the_rgcn_header():
     for name in declared:
         assert getattr(lib, name).argtypes == _hip.RGCN_PROTOTYPES[name][1]
     assert _hip.RGCN_PROTOTYPES["gcm_dense_rgcnconv_fwd_workspace_bytes"][0] is ctypes.c_size_t
-    assert lib.gcm_abi_version() == 7                               # the section is additive
+    assert lib.gcm_abi_version() == 8                               # the section is additive
 
 
 def test_c_abi_validates_without_a_device():

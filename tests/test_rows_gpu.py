@@ -883,7 +883,8 @@ def test_rows_colcache_c_abi_four_and_eight_waves(kind):
     def chain(form):
         nodes, adj = torch.zeros(B, N, F, device=DEV), torch.zeros(B, N, N, device=DEV)
         count = torch.zeros(B, dtype=torch.int64, device=DEV)
-        cA, cR = torch.full((B, N, F), float("nan"), device=DEV), torch.full((B, N, H), float("nan"), device=DEV)
+        cA = torch.full((B, N, F), float("nan"), device=DEV, dtype=torch.float64)      # (the agg1 cache is float64)
+        cR = torch.full((B, N, H), float("nan"), device=DEV)
         out = []
         for t in range(T):
             saved = torch.zeros(lay[0], device=DEV)

@@ -189,5 +189,5 @@ def test_segment_section_of_the_abi():
         "gcm_sparse_seg_plan", "gcm_sparse_seg_rows", "gcm_sparse_seg_nodes", "gcm_sparse_seg_edges_plan",
         "gcm_sparse_seg_edges", "gcm_sparse_seg_final_T"}
     assert not declared & set(_hip.PROTOTYPES) and not declared & set(_hip.WINDOW_PROTOTYPES)
-    assert _hip._CONSTANTS["GCM_ABI_VERSION"] == 7
+    assert _hip._CONSTANTS["GCM_ABI_VERSION"] == 8
     assert _hip.SPARSE_SEG_CHUNK == 1024 and _hip.SPARSE_SEG_ROWS == 6 and _hip.SPARSE_SEG_TOTALS == 4

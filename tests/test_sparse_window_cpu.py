@@ -181,4 +181,4 @@ def test_window_section_of_the_abi():
     assert declared == set(_hip.WINDOW_PROTOTYPES) == {"gcm_sparse_drop_plan", "gcm_sparse_drop_nodes",
                                                        "gcm_sparse_drop_edges", "gcm_sparse_drop_values_bwd"}
     assert not declared & set(_hip.PROTOTYPES)
-    assert _hip._CONSTANTS["GCM_ABI_VERSION"] == 7 and _hip.SPARSE_DROP_CHUNK == 1024
+    assert _hip._CONSTANTS["GCM_ABI_VERSION"] == 8 and _hip.SPARSE_DROP_CHUNK == 1024

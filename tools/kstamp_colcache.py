@@ -26,7 +26,7 @@ count = torch.zeros(B, dtype=torch.int64, device=dev)
 obs = torch.rand(B, F, device=dev)
 P = 2 * H * F + H + 2 * H * H + H
 params = torch.randn(P, device=dev) * 0.1
-cA, cR = torch.rand(B, N, F, device=dev), torch.rand(B, N, H, device=dev)
+cA, cR = torch.rand(B, N, F, device=dev, dtype=torch.float64), torch.rand(B, N, H, device=dev)   # (agg1: float64)
 lay = (ctypes.c_size_t * 8)()
 _hip.lib().gcm_dense_rows_layout(B, N, F, H, H, ctypes.addressof(lay))
 saved = torch.empty(lay[0], device=dev)
